@@ -21,8 +21,14 @@ to host).  Other configs: --workload groupby (config 3), filter (config 2), sort
 Prints ONE JSON line on rank 0 (contract in the task statement), with
   roofline     — the dominant kernel's algorithmic bytes / its mean device time
                  (hipEvents on the launch stream, via nut_ctx_kernel_time)
-  cpu_baseline — the C oracle (oracle/, OpenMP over the host cores) on a bounded
-                 sample of the same workload, rank 0 at N=1 only.
+A plain run sets up, warms up, times the steps and prints that line.  --full adds what
+takes runs of its own, after the timed loop:
+  roofline.copy_floor / config.launch_shape — the in-build streaming probe and the Q1
+                 kernel's candidate launch shapes (--no-copy-floor skips both)
+  cpu_baseline, parity — the C oracle (oracle/, OpenMP over the host cores) on a bounded
+                 sample of the same workload and the GPU result checked against it,
+                 rank 0 at N=1 only (--no-cpu-baseline skips both); exit 1 on a mismatch.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float64).
 """
 from __future__ import annotations
 
@@ -58,14 +64,26 @@ def parse():
     p.add_argument("--selectivity", type=float, default=0.5, help="filter: fraction selected")
     p.add_argument("--key-range", type=float, default=None, metavar="FRACTION",
                    help="sort: keys uniform over this fraction of the int64 range (a sample-sort rank's share)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-copy-floor", action="store_true", help="skip the in-run device-copy floor probe")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the copy-floor probe, the Q1 launch-shape runs and the "
+                        "CPU baseline with its parity check (a plain run times the steps and nothing else)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned as DIR/<name>.npy (float64; a fixed, seeded "
+                        "row sample when the result is larger than DUMP_BYTES); single process only")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
+    p.add_argument("--no-copy-floor", action="store_true",
+                   help="with --full: skip the in-run device-copy floor probe and the launch-shape runs")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline work")
     p.add_argument("--dist", action="store_true",
                    help="run N=1 through nut_dist_* too (one RCCL rank), as the N>1 runs do")
     p.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                    help="nut_ctx_set_option for A/B runs (Executor.OPTIONS names); recorded in config")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:  # a plain run: nothing beside the timed steps
+        args.no_cpu_baseline = args.no_copy_floor = True
+    if args.dump_outputs and args.workload == "parse":
+        p.error("--dump-outputs: the parse workload returns no arrays")
+    return args
 
 
 # ------------------------------------------------------------------ workloads
@@ -572,6 +590,60 @@ def _cmp_groups(gk, gw, ck, cw, f64_cols, rtol):
     return r
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 48 << 20  # of float64 values in all (the .npy headers are a few hundred bytes)
+DUMP_SEED = 0x6E7574
+
+
+def step_outputs(workload: str, r):
+    """What one step of `workload` returned, as [(name, array or tensor [rows, ...], kind)]:
+    kind "f64" = float64 values, "int" = integers below 2^53 (counts, row ids, codes; exact
+    in float64), "i64" = full-range int64 (written as <name>_hi / <name>_lo, the signed high
+    and unsigned low 32 bits, so that float64 holds them exactly)."""
+    if workload in ("q1", "groupby"):  # (keys int64 [G, nk], words uint64 [G, na]) ordered by key
+        keys, words = r
+        if workload == "q1":
+            return [("keys", keys, "int"), ("sums", np.ascontiguousarray(words[:, :3]).view(np.float64), "f64"),
+                    ("count", words[:, 3], "int")]
+        return [("keys", keys, "i64"), ("sums", np.ascontiguousarray(words[:, :1]).view(np.float64), "f64")]
+    if workload == "filter":  # (out, out_n) in HBM: the selected values in row order and their count
+        out, out_n = r
+        n = int(out_n.item())
+        return [("count", np.array([n]), "int"), ("selected", out[:n], "i64")]
+    if workload in ("scanexpr", "sort"):  # one int64 tensor in HBM
+        return [("selected" if workload == "scanexpr" else "sorted", r, "i64")]
+    if workload == "join":  # (probe_idx, build_idx) in HBM, ordered by probe row
+        return [("probe_idx", r[0], "int"), ("build_idx", r[1], "int")]
+    # q12expr, q12join: {output name: numpy array} in SELECT-list order (codes and counts)
+    return [(name, a, "f64" if a.dtype.kind == "f" else "int") for name, a in r.items()]
+
+
+def dump_outputs(path: Path, outs):
+    """Write `outs` (step_outputs) as path/<name>.npy, float64.  When they hold more than
+    DUMP_BYTES, every array longer than its share is cut to a sample of its rows: ascending
+    row numbers drawn with DUMP_SEED from the array's length, the same for every run that
+    returns as many rows."""
+    path.mkdir(parents=True, exist_ok=True)
+    width = lambda a, kind: (int(np.prod(a.shape[1:])) if a.ndim > 1 else 1) * (2 if kind == "i64" else 1)
+    cap = (DUMP_BYTES // 8) // max(sum(width(a, kind) for _, a, kind in outs), 1)
+    written = {}
+    for name, a, kind in outs:
+        rows = a.shape[0]
+        if rows > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, rows, size=cap))
+            a = a[torch.from_numpy(idx).to(a.device)] if torch.is_tensor(a) else a[idx]
+        a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        if kind == "i64":
+            a = a.astype(np.int64, copy=False)
+            parts = {f"{name}_hi": (a >> 32).astype(np.float64), f"{name}_lo": (a & 0xFFFFFFFF).astype(np.float64)}
+        else:
+            parts = {name: a.astype(np.float64)}
+        for k, v in parts.items():
+            np.save(path / f"{k}.npy", v)
+            written[k] = {"rows_written": int(v.shape[0]), "rows": int(rows)}
+    return written
+
+
 # ------------------------------------------------------------------ main
 def parse_bench(args):
     """BASELINE config 1: parse-only over the reference's SQL fixtures (tests/golden/sql:
@@ -623,6 +695,9 @@ def main():
         if world == 1 and args.gpus > 1:
             print("bench.py: --gpus N>1 must be launched with torch.distributed.run", file=sys.stderr)
             sys.exit(2)
+    if args.dump_outputs and (world > 1 or args.dist):
+        print("bench.py: --dump-outputs takes a single-process run (no --dist, --gpus 1)", file=sys.stderr)
+        sys.exit(2)
     torch.cuda.set_device(local_rank)
     from nutdb_amd import Executor
     ex = Executor(local_rank)
@@ -684,6 +759,9 @@ def main():
     if gb_stats is not None and gb_stats["path"] == "partitioned_ordered":
         gb_stats["overflow_rows"] = ex.groupby_overflow_rows()
         gb_stats["heavy_keys"], gb_stats["heavy_rows"] = ex.groupby_heavy()
+    dumped = None
+    if args.dump_outputs:  # the last timed step's result, before anything else runs
+        dumped = dump_outputs(Path(args.dump_outputs), step_outputs(args.workload, last[0]))
     if nd is not None:
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -814,6 +892,8 @@ def main():
                          "traffic_source": traffic_src,
                          "copy_floor": copy_floor},
         }
+        if dumped is not None:
+            line["outputs"] = dumped
         if cpu is not None:
             line["cpu_baseline"] = cpu
             line["parity"] = parity

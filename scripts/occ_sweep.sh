@@ -9,7 +9,7 @@ rounds=$1; cfgs=$2; shift 2
 for round in $(seq 1 "$rounds"); do
   for cfg in $cfgs; do
     bd=${cfg%%:*}; bl=${cfg##*:}
-    timeout -k 10 200 python bench.py "$@" --no-cpu-baseline --option priv_bd=$bd --option priv_blocks=$bl \
+    timeout -k 10 200 python bench.py "$@" --full --no-cpu-baseline --option priv_bd=$bd --option priv_blocks=$bl \
       2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -18,7 +18,7 @@ else
     python3 bench.py "$@" --no-cpu-baseline > "$out/trace.log" 2>&1 || { tail -5 "$out/trace.log"; exit 1; }
   cp "$out/trace/trace_kernel_stats.csv" "$out/kernel_stats.csv" || exit 1
 fi
-timeout -k 10 300 python3 bench.py "$@" > "$out/bench.log" 2>&1 || { tail -5 "$out/bench.log"; exit 1; }
+timeout -k 10 300 python3 bench.py "$@" --full > "$out/bench.log" 2>&1 || { tail -5 "$out/bench.log"; exit 1; }
 grep '^{' "$out/bench.log" | tail -1 > "$out/bench.json"
 python3 - "$out/bench.json" "$name" <<'PY'
 import json, sys
