@@ -243,7 +243,8 @@ typedef enum {
  *   arithmetic  i64 (+ - *) wraps; any f64 operand makes the op f64; DIV is always
  *            f64 (int operands converted); MOD/INTDIV on ints truncate toward zero and
  *            fail the query on a zero divisor (INT64_MIN % -1 = 0, INT64_MIN div -1
- *            wraps); MOD on f64 is fmod
+ *            wraps); MOD on f64 is fmod.  f64 DIV / MOD never fail: x / 0 = +-inf; 0 / 0,
+ *            x mod 0 and inf mod y = the negative quiet NaN; a NaN operand passes quieted
  *   compare  bool; an int compared with an f64 converts the int to f64
  *   AND OR XOR NOT  bool operands (ints: non-zero = true), no short circuit
  *   BITAND BITOR BITXOR BITNOT SHL SHR  ints; shift counts outside [0, 63] give 0

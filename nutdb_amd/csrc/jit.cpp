@@ -100,7 +100,7 @@ struct Gen {
         }
         case NUT_P_DIV: r = {NUT_PT_F64, "(" + as_f(a[0]) + " / " + as_f(a[1]) + ")"}; break;
         case NUT_P_MOD:
-          if (f) r = {NUT_PT_F64, "fmod(" + as_f(a[0]) + ", " + as_f(a[1]) + ")"};
+          if (f) r = {NUT_PT_F64, "jfmod(" + as_f(a[0]) + ", " + as_f(a[1]) + ")"};
           else r = {NUT_PT_I64, "jmod(" + as_i(a[0]) + ", " + as_i(a[1]) + ", err)"};
           break;
         case NUT_P_INTDIV:
@@ -217,6 +217,17 @@ __device__ __forceinline__ int64_t jshr(int64_t a, int64_t b) {
   return (b >= 0 && b < 64) ? (a >> b) : (a < 0 ? -1 : 0);
 }
 __device__ __forceinline__ int64_t jabs(int64_t a) { return a < 0 ? (int64_t)(0 - (uint64_t)a) : a; }
+// f64 MOD: C fmod with the NaN rule of f64 DIV on this device (include/nutexec.h): a NaN
+// operand passes through quieted, the first operand's first; an invalid operation (x mod 0,
+// inf mod y) gives the negative quiet NaN, as 0 / 0 does.  The device library's fmod returns
+// +qNaN for all of these, and MIN / MAX order NaNs by sign.
+__device__ __forceinline__ double jfmod(double a, double b) {
+  const double r = fmod(a, b);
+  if (r == r) return r;
+  if (a != a) return as_f64(as_u64(a) | 0x0008000000000000ull);
+  if (b != b) return as_f64(as_u64(b) | 0x0008000000000000ull);
+  return as_f64(0xFFF8000000000000ull);
+}
 // byte-table membership; an empty table (n == 0) is never read
 __device__ __forceinline__ bool jlookup(int64_t x, uint64_t t, uint64_t n) {
   if ((uint64_t)x >= n) return false;

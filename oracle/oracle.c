@@ -209,14 +209,22 @@ static grp_t *tbl_find(table_t *t, const orc_agg_spec *s, const int64_t *k) {
   return g;
 }
 
+/* Non-finite data follows IEEE: once the running sum is non-finite (an operand is, or the
+ * add overflowed) the compensation term is left alone — (x - t) + sum would be inf - inf —
+ * and the result is the running sum itself (f64_sum_out).  A finite t has finite operands,
+ * so finite, non-overflowing input takes exactly the compensated steps. */
 static void neumaier_add(double *sum, double *comp, double x) {
   double t = *sum + x;
-  if (fabs(*sum) >= fabs(x))
-    *comp += (*sum - t) + x;
-  else
-    *comp += (x - t) + *sum;
+  if (isfinite(t)) {
+    if (fabs(*sum) >= fabs(x))
+      *comp += (*sum - t) + x;
+    else
+      *comp += (x - t) + *sum;
+  }
   *sum = t;
 }
+
+static double f64_sum_out(double sum, double comp) { return isfinite(sum) ? sum + comp : sum; }
 
 static double eval_f64(const orc_agg_spec *s, int a, uint64_t i) {
   const double *c0 = (const double *)s->val_col[s->agg_arg[a][0]];
@@ -293,7 +301,7 @@ static void grp_merge(grp_t *dst, const grp_t *src, const orc_agg_spec *s) {
     }
     if (op == ORC_AGG_SUM) {
       neumaier_add(&dst->sumf[a], &dst->comp[a], src->sumf[a]);
-      dst->comp[a] += src->comp[a];
+      if (isfinite(dst->sumf[a])) dst->comp[a] += src->comp[a];
     } else if (op == ORC_AGG_MIN) { if (src->w[a] < dst->w[a]) dst->w[a] = src->w[a]; }
     else { if (src->w[a] > dst->w[a]) dst->w[a] = src->w[a]; }
   }
@@ -321,7 +329,7 @@ static void grp_out(const grp_t *g, const orc_agg_spec *s, int64_t *ok, uint64_t
     if (op != ORC_AGG_COUNT && !agg_is_i64(s, a)) {
       double d;
       if (op == ORC_AGG_SUM) {
-        d = g->sumf[a] + g->comp[a];
+        d = f64_sum_out(g->sumf[a], g->comp[a]);
       } else {
         uint64_t b = (w >> 63) ? (w & 0x7FFFFFFFFFFFFFFFull) : ~w;
         memcpy(&d, &b, 8);

@@ -87,7 +87,11 @@ typedef struct {
  * word: f64 bits for SUM/MIN/MAX over f64, int64 for COUNT and i64 SUM/MIN/MAX
  * (i64 SUM wraps two's complement).  out_keys[g*nkeys + j], out_aggs[g*naggs + a].
  * Returns number of groups, or UINT64_MAX if cap is too small.
- * f64 sums are Neumaier-compensated (≈ correctly rounded). nthreads<=0: all cores. */
+ * f64 sums are Neumaier-compensated (≈ correctly rounded) while they are finite; once a
+ * running sum is not (a NaN or infinite value, or an overflow) it follows IEEE: +inf for
+ * one sign of infinity, NaN for both or for a NaN — the compensation is dropped
+ * (tests/test_oracle_nonfinite_cpu.py).  f64 MIN / MAX: the total order -NaN < -inf < ... <
+ * -0.0 < +0.0 < ... < +inf < +NaN on the bits, payloads included.  nthreads<=0: all cores. */
 uint64_t orc_groupby(const orc_agg_spec *spec, uint64_t cap, int64_t *out_keys,
                      uint64_t *out_aggs, int nthreads);
 /* The same result by one fixed method: per-thread tables over the row chunks, merged into

@@ -222,6 +222,7 @@ COMPILE_CASES = [
      "group by k, j", {"x": "float64", "y": "int64"}),
     ("select sum(multiIf(a = 1, b, a = 2, 2 * b, 0)), count(case a when 1 then 1 when 2 then 1 end) from t "
      "where a is not null", {"a": "int64", "b": "float64"}),
+    ("select k, max(x % y), min(x / y), sum(x % 2) from t group by k", {"x": "float64", "y": "float64"}),  # jfmod
 ]
 
 

@@ -32,7 +32,9 @@ def dev(x, ex):
 class Gen:
     """Random typed expression trees as RPN.  Divisors are made non-zero (x | 1,
     abs(y) + 1.0) so the fuzz compares values; zero divisors have their own test.
-    No op can produce NaN (values stay finite), so f64 MIN/MAX compare bit-exactly."""
+    No op can produce NaN (values stay finite), so f64 MIN/MAX compare bit-exactly.
+    What this excludes — f64 division and fmod by zero, NaN / inf / subnormal operands,
+    comparisons with a NaN, IF with a NaN branch — is tests/test_gpu_nonfinite.py's."""
 
     def __init__(self, rng, icols, fcols):
         self.r, self.ic, self.fc = rng, icols, fcols
