@@ -217,7 +217,28 @@ nut_status nut_filter_i64_async(nut_ctx *ctx, const int64_t *col, uint64_t n, in
  * Lowered from WhereClause (AND-chain of `col op literal`), GroupByClause.keys
  * (identifiers) and the SELECT list's FnCall{Others("sum"|"count"|"min"|"max")}.
  * ------------------------------------------------------------------------ */
-typedef enum { NUT_T_I64 = 0, NUT_T_F64 = 1, NUT_T_STR = 2 /* result columns of typed tables only */ } nut_type;
+typedef enum {
+  NUT_T_I64 = 0, NUT_T_F64 = 1, NUT_T_STR = 2 /* result columns of typed tables only */,
+  /* Physical (narrow) column types: how a column is stored, never how it is computed.
+   * Integers execute as int64 (I*: sign-extended, U*: zero-extended), F32 as float64
+   * (widened exactly, denormals kept).  They are accepted where a kernel loads the column
+   * itself — nut_agg_spec.prog_col_type[] in expression mode (nut_groupby,
+   * nut_groupby_accumulate, nut_groupby_to_host, nut_select_rows, nut_eval_rows and the
+   * *_jit_compile / jit_source calls) and nut_gather_typed — and nowhere else: fused mode
+   * (pred_type, val_type) and keys[] stay int64 / float64 (NUT_ERR_INVALID_ARG otherwise),
+   * and so do the sort / filter / join entry points — widen a column for those with
+   * nut_gather_typed(idx = NULL).  SQL plans take them in nut_column.type (nut_plan_route,
+   * nut_plan_prepare, nut_plan_execute*; NUT_COL_HOST copies width x nrows bytes): a
+   * single-table plan over a narrow column runs in expression mode (never a fused route),
+   * scans carry projections and ORDER BY keys through the row ids with nut_gather_typed, and
+   * JOIN plans widen their narrow columns first (one extra pass).
+   * A narrow GROUP BY key is passed as the one-node key_prog {NUT_P_COL c}.  nut_prog_type,
+   * result words and every program semantic are unchanged: a narrow column type-checks as
+   * int64 / float64 and outputs are NUT_T_I64 / NUT_T_F64. */
+  NUT_T_I32 = 3, NUT_T_I16 = 4, NUT_T_I8 = 5,
+  NUT_T_U32 = 6, NUT_T_U16 = 7, NUT_T_U8 = 8,
+  NUT_T_F32 = 9
+} nut_type;
 typedef enum { NUT_AGG_SUM = 0, NUT_AGG_COUNT = 1, NUT_AGG_MIN = 2, NUT_AGG_MAX = 3 } nut_agg_op;
 typedef enum {
   NUT_EX_COL = 0,       /* v[a]                      (i64 or f64 column) */
@@ -319,7 +340,9 @@ typedef struct {
   int32_t prog_mode;
   int32_t nprog_cols;
   const void *prog_col[NUT_MAX_PROG_COLS];
-  int32_t prog_col_type[NUT_MAX_PROG_COLS]; /* nut_type */
+  int32_t prog_col_type[NUT_MAX_PROG_COLS]; /* nut_type: I64, F64 or a narrow physical type
+                                               (NUT_T_I32 .. NUT_T_F32; the column is then
+                                               n values of that width, aligned to it) */
   nut_prog where;                           /* n = 0: every row */
   nut_prog agg_val[NUT_MAX_AGGS];           /* argument of each non-COUNT aggregate */
   nut_prog agg_mask[NUT_MAX_AGGS];          /* n = 0: every row; else the aggregate takes
@@ -491,6 +514,13 @@ nut_status nut_hash_partition_i64(nut_ctx *ctx, const int64_t *keys, uint64_t n,
  * not overlap src. */
 nut_status nut_gather_u64(nut_ctx *ctx, const uint64_t *src, const int64_t *idx, uint64_t n, uint64_t null_bits,
                           uint64_t *out);
+/* The same through a column of any physical type (src_type: nut_type, NUT_T_STR excluded):
+ * out[i] = the widened 8-byte word of src[idx[i]] (sign / zero extension, F32 -> float64
+ * bits), or `null_bits` where idx[i] < 0.  idx NULL: rows 0..n-1, a pure widening pass.
+ * src must be aligned to its type's width and must not overlap out.  For NUT_T_I64 /
+ * NUT_T_F64 this is nut_gather_u64. */
+nut_status nut_gather_typed(nut_ctx *ctx, const void *src, int src_type, const int64_t *idx, uint64_t n,
+                            uint64_t null_bits, uint64_t *out);
 
 /* ========================================================================
  * Multi-GPU execution over RCCL (SURVEY.md §8(b) nut_dist_*, §8(e)).
@@ -725,6 +755,13 @@ nut_status nut_table_column_info(const nut_table *t, int j, const char **name, i
  * rows every column has. */
 nut_status nut_table_append(nut_ctx *ctx, nut_table *t, int j, const void *data, const int64_t *offsets,
                             uint64_t n);
+/* on != 0: Int8/16/32, UInt8/16/32, Float32 and Boolean (as UInt8) columns keep their
+ * declared width in HBM — nut_table_append copies them straight into place, no widening
+ * pass — and nut_table_column_info reports the narrow exec_type (NUT_T_I32 ...); Int64,
+ * UInt64, Date / Datetime, String / Enum codes and Float64 stay 8 B.  Plans execute the
+ * same either way.  Only while the table has no rows (else
+ * NUT_ERR_INVALID_ARG); the default is off. */
+nut_status nut_table_set_narrow(nut_table *t, int on);
 /* Execute a plan against the table (binds every plan column by name). */
 nut_status nut_table_execute(nut_ctx *ctx, nut_table *t, const nut_plan *plan, uint64_t group_hint,
                              nut_result **out);

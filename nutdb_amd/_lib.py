@@ -40,6 +40,9 @@ STATUS_NAMES = {
 GEN_U62, GEN_FULL_I64, GEN_POOL_KEY, GEN_DYADIC, GEN_UNIT_F64, GEN_RANGE_I64, GEN_RANGE_F64, GEN_SKEW_KEY = range(8)
 LT, LE, GT, GE, EQ, NE, IN, NOT_IN = range(8)
 T_I64, T_F64, T_STR = 0, 1, 2
+# physical (narrow) column types: stored width, executed as int64 / float64
+T_I32, T_I16, T_I8, T_U32, T_U16, T_U8, T_F32 = 3, 4, 5, 6, 7, 8, 9
+TYPE_WIDTH = {T_I64: 8, T_F64: 8, T_I32: 4, T_I16: 2, T_I8: 1, T_U32: 4, T_U16: 2, T_U8: 1, T_F32: 4}
 COL_KINDS = ["int", "uint", "float", "bool", "date", "datetime", "string", "enum"]
 KERNEL_FILTER, KERNEL_AGGREGATE, KERNEL_SORT = 0, 1, 2
 AGG_SUM, AGG_COUNT, AGG_MIN, AGG_MAX = range(4)
@@ -146,6 +149,7 @@ SIGNATURES = {
     "nut_join_free": (None, [_P]),
     "nut_hash_partition_i64": (_I32, [_P, _P, _U64, _I32, _I64, _P, _P, C.POINTER(_U64)]),
     "nut_gather_u64": (_I32, [_P, _P, _P, _U64, _U64, _P]),
+    "nut_gather_typed": (_I32, [_P, _P, _I32, _P, _U64, _U64, _P]),
     "nut_select_rows": (_I32, [_P, C.POINTER(NutAggSpec), _P, C.POINTER(_U64)]),
     "nut_select_jit_compile": (_I32, [C.POINTER(NutAggSpec)]),
     "nut_eval_rows": (_I32, [_P, C.POINTER(NutAggSpec), _P, _U64, _P, _P]),
@@ -169,6 +173,7 @@ SIGNATURES = {
     "nut_table_execute": (_I32, [_P, _P, _P, _U64, C.POINTER(_P)]),
     "nut_table_execute2": (_I32, [_P, _P, _P, _P, _U64, C.POINTER(_P)]),
     "nut_table_executen": (_I32, [_P, C.POINTER(_P), _I32, _P, _U64, C.POINTER(_P)]),
+    "nut_table_set_narrow": (_I32, [_P, _I32]),
     "nut_table_free": (None, [_P]),
     "nut_groups_size": (_I32, [_P, C.POINTER(_U64)]),
     "nut_groups_to_host": (_I32, [_P, _P, _P, _U64]),

@@ -197,7 +197,8 @@ __device__ constexpr int key_prog_mask() {
   else return 0;
 }
 
-// VEC: 1 = all columns 16-B aligned (vector loads), 0 = decided at run time (p.vec)
+// VEC: 1 = all columns 16-B aligned (vector loads), 0 = decided at run time (p.vec; shapes
+// with narrow columns decide per column, load_cols_typed)
 template <int VEC>
 __device__ __forceinline__ void load2(const AggArgs &p, const uint64_t *col, uint64_t i, uint64_t &x, uint64_t &y) {
   if (VEC == 1 || p.vec) {
@@ -212,6 +213,35 @@ __device__ __forceinline__ void load2(const AggArgs &p, const uint64_t *col, uin
   }
 }
 
+// Program columns C.. of a shape with narrow columns (shape_narrow): each is read at its
+// stored width and widened; the row layout is the 8-byte one, so a pair of rows of a
+// column of width w is one 2w-byte load where its base allows it (bit C of p.vec), else
+// one load per row.
+template <class S, bool TAIL, int C = 0>
+__device__ __forceinline__ void load_cols_typed(const AggArgs &p, uint64_t i0, uint64_t i1, uint64_t nend,
+                                                Rows<S> &x) {
+  if constexpr (C < S::MV) {
+    constexpr int T = col_type<S>(C);
+    const uint64_t *col = p.val_col[C];
+    uint64_t(&d)[4] = x.vv[C];
+    if (TAIL) {
+      d[0] = i0 < nend ? load_word<T, false>(col, i0) : 0;
+      d[1] = i0 + 1 < nend ? load_word<T, false>(col, i0 + 1) : 0;
+      d[2] = i1 < nend ? load_word<T, false>(col, i1) : 0;
+      d[3] = i1 + 1 < nend ? load_word<T, false>(col, i1 + 1) : 0;
+    } else if ((p.vec >> C) & 1) {
+      load_pair<T>(col, i0, d[0], d[1]);
+      load_pair<T>(col, i1, d[2], d[3]);
+    } else {
+      d[0] = load_word<T, false>(col, i0);
+      d[1] = load_word<T, false>(col, i0 + 1);
+      d[2] = load_word<T, false>(col, i1);
+      d[3] = load_word<T, false>(col, i1 + 1);
+    }
+    load_cols_typed<S, TAIL, C + 1>(p, i0, i1, nend, x);
+  }
+}
+
 // rows {i0, i0+1, i1, i1+1}; TAIL: guard every row against n
 template <int NK, class S, int VEC, bool TAIL>
 __device__ __forceinline__ void load_rows(const AggArgs &p, uint64_t i0, uint64_t i1, uint64_t nend, Rows<S> &x) {
@@ -221,6 +251,13 @@ __device__ __forceinline__ void load_rows(const AggArgs &p, uint64_t i0, uint64_
       d[1] = i0 + 1 < nend ? col[i0 + 1] : 0;
       d[2] = i1 < nend ? col[i1] : 0;
       d[3] = i1 + 1 < nend ? col[i1 + 1] : 0;
+    } else if constexpr (shape_narrow<S>()) {  // p.vec is a mask: the plain key columns' bit
+      if ((p.vec >> kVecKeys) & 1) {
+        load_pair<NUT_T_I64>(col, i0, d[0], d[1]);
+        load_pair<NUT_T_I64>(col, i1, d[2], d[3]);
+      } else {
+        d[0] = col[i0], d[1] = col[i0 + 1], d[2] = col[i1], d[3] = col[i1 + 1];
+      }
     } else {
       load2<VEC>(p, col, i0, d[0], d[1]);
       load2<VEC>(p, col, i1, d[2], d[3]);
@@ -237,9 +274,13 @@ __device__ __forceinline__ void load_rows(const AggArgs &p, uint64_t i0, uint64_
     ld(p.keys[0], x.k1);
   }
   if (NK == 2 && !(KP & 2)) ld(p.keys[1], x.k2);
+  if constexpr (shape_narrow<S>()) {
+    load_cols_typed<S, TAIL>(p, i0, i1, nend, x);
+  } else {
 #pragma unroll
-  for (int c = 0; c < S::MV; ++c)
-    if (c < S::nv(p)) ld(p.val_col[c], x.vv[c]);
+    for (int c = 0; c < S::MV; ++c)
+      if (c < S::nv(p)) ld(p.val_col[c], x.vv[c]);
+  }
 }
 
 // ------------------------------------------------------------------ spill (partitioned mode)

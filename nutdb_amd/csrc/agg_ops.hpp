@@ -42,7 +42,10 @@ struct AggArgs {
   uint32_t lds_limit;             // claims admitted before the table closes
   int32_t lds_log2;
   int32_t priv;                   // private groups per thread (PRIV kernels)
-  int32_t vec;                    // all columns 16-B aligned: vector loads
+  int32_t vec;                    // all columns 16-B aligned: vector loads (a truth value).  Generated
+                                  // shapes with a narrow column (shape_narrow) read it as a mask instead:
+                                  // bit c = column c's pairs are one load, bit kVecKeys = the key columns';
+                                  // only launch_agg's expression-mode branch sets and launches that form
   int32_t nokey;                  // global aggregate: no key column, every key is 0
   int32_t pred_nset[NUT_MAX_PRED];                 // NUT_IN / NUT_NOT_IN set sizes
   uint64_t pred_set[NUT_MAX_PRED][NUT_MAX_SET];    // set values (bits)
@@ -88,6 +91,34 @@ struct NoProg {
   template <class V>
   __device__ static bool valid(const AggArgs &, int, const V &, int, bool &) { return true; }
 };
+
+// Physical type of program column c (nut_type; common.hpp type_width): generated shapes
+// carry them in kColTypes, 4 bits per column; every other shape reads 8-byte columns.
+template <class S>
+__host__ __device__ constexpr int col_type(int c) {
+  if constexpr (S::kProg) return (int)((S::kColTypes >> (4 * c)) & 15u);
+  else return NUT_T_I64;
+}
+// a shape with a column narrower than 8 bytes: its loads go through load_word / load_pair
+// and AggArgs::vec is a mask (bit c: column c's base is aligned to 2 x its width, so a pair
+// of rows is one load; bit 16: the plain key columns are 16-B aligned)
+template <class S>
+__host__ __device__ constexpr bool shape_narrow() {
+  for (int c = 0; c < S::MV; ++c)
+    if (type_width(col_type<S>(c)) < 8) return true;
+  return false;
+}
+constexpr int kVecKeys = 16;
+
+// one row of every program column, widened (the scan and projection kernels)
+template <class S, bool NT, int C = 0>
+__device__ __forceinline__ void load_row_typed(const uint64_t *const *cols, uint64_t r, bool ok,
+                                               uint64_t (&vv)[S::MV > 0 ? S::MV : 1][1]) {
+  if constexpr (C < S::MV) {
+    vv[C][0] = ok ? load_word<col_type<S>(C), NT>(cols[C], r) : 0;
+    load_row_typed<S, NT, C + 1>(cols, r, ok, vv);
+  }
+}
 
 struct Generic : NoProg {
   static constexpr int MP = NUT_MAX_PRED, MV = NUT_MAX_VALS, MA = NUT_MAX_AGGS;

@@ -73,19 +73,28 @@ nut_status validate(const nut_agg_spec *s) {
       if (s->pred_op[t] >= NUT_IN && (s->pred_nset[t] < 1 || s->pred_nset[t] > NUT_MAX_SET))
         return fail(NUT_ERR_INVALID_ARG, "nut_groupby: IN sets hold 1..16 values");
       if (s->pred_type[t] != NUT_T_I64 && s->pred_type[t] != NUT_T_F64)
-        return fail(NUT_ERR_INVALID_ARG, "nut_groupby: bad predicate type");
+        return fail(NUT_ERR_INVALID_ARG, "nut_groupby: bad predicate type: predicate column " + std::to_string(t) +
+                                             " has type " + std::to_string(s->pred_type[t]) +
+                                             " (fused mode reads int64 / float64 columns; narrow columns need prog_mode = 1)");
     }
     for (int c = 0; c < s->nvals; ++c)
       if (!s->val_col[c]) return fail(NUT_ERR_INVALID_ARG, "nut_groupby: NULL value column");
   }
+  if (!s->prog_mode)
+    for (int c = 0; c < s->nvals; ++c)
+      if (type_known(s->val_type[c]) && type_width(s->val_type[c]) < 8)
+        return fail(NUT_ERR_INVALID_ARG, "nut_groupby: value column " + std::to_string(c) + " has narrow type " +
+                                             std::to_string(s->val_type[c]) +
+                                             " (fused mode reads int64 / float64 columns; narrow columns need prog_mode = 1)");
   if (s->prog_mode) {
     if (s->npred || s->nvals) return fail(NUT_ERR_INVALID_ARG, "nut_groupby: expression mode takes no pred_*/val_* terms");
     if (s->nprog_cols < 0 || s->nprog_cols > NUT_MAX_PROG_COLS)
       return fail(NUT_ERR_UNSUPPORTED, "nut_groupby: expression programs read at most 16 columns");
     for (int c = 0; c < s->nprog_cols; ++c) {
       if (s->n && !s->prog_col[c]) return fail(NUT_ERR_INVALID_ARG, "nut_groupby: NULL program column");
-      if (s->prog_col_type[c] != NUT_T_I64 && s->prog_col_type[c] != NUT_T_F64)
-        return fail(NUT_ERR_INVALID_ARG, "nut_groupby: bad program column type");
+      if (!type_known(s->prog_col_type[c])) return fail(NUT_ERR_INVALID_ARG, "nut_groupby: bad program column type");
+      if (!type_aligned(s->prog_col[c], s->prog_col_type[c]))
+        return fail(NUT_ERR_INVALID_ARG, "nut_groupby: program column " + std::to_string(c) + " is not aligned to its type");
     }
     int32_t t;
     for (int k = 0; k < s->nkeys; ++k) {
@@ -377,6 +386,17 @@ nut_status launch_agg(nut_groups *g, const nut_agg_spec *s, uint64_t group_hint,
   for (int t = 0; t < a.npred; ++t) bad |= misaligned(a.pred_col[t]);
   for (int v = 0; v < a.nvals; ++v) bad |= misaligned(a.val_col[v]);
   a.vec = bad ? 0 : 1;  // 8-B aligned columns (e.g. slices) take two 8-B loads per pair
+  bool narrow = false;
+  for (int v = 0; s->prog_mode && v < s->nprog_cols; ++v) narrow |= type_width(s->prog_col_type[v]) < 8;
+  if (narrow) {
+    // a shape with narrow columns decides per column (agg_ops.hpp shape_narrow): bit v = the
+    // pair of rows of column v is one load (base aligned to 2 x width), bit kVecKeys = the
+    // plain key columns are 16-B aligned
+    uint32_t m = misaligned(a.keys[0]) || misaligned(a.keys[1]) ? 0u : 1u << kVecKeys;
+    for (int v = 0; v < s->nprog_cols; ++v)
+      if (((uintptr_t)a.val_col[v] & (uintptr_t)(2 * type_width(s->prog_col_type[v]) - 1)) == 0) m |= 1u << v;
+    a.vec = (int32_t)m;
+  }
 
   const size_t lds_max = kAggLdsMax;
   const int na = s->naggs;
@@ -2130,6 +2150,9 @@ nut_status nut_select_rows(nut_ctx *c, const nut_agg_spec *s, int64_t *out_rows,
   *count_host = 0;
   for (int i = 0; i < s->nprog_cols; ++i)
     if (s->n && !s->prog_col[i]) return fail(NUT_ERR_INVALID_ARG, "nut_select_rows: NULL program column");
+  for (int i = 0; i < s->nprog_cols; ++i)
+    if (type_known(s->prog_col_type[i]) && !type_aligned(s->prog_col[i], s->prog_col_type[i]))
+      return fail(NUT_ERR_INVALID_ARG, "nut_select_rows: program column " + std::to_string(i) + " is not aligned to its type");
   nut_agg_spec q = *s;  // the WHERE program alone
   q.naggs = 0;
   int32_t kinds[NUT_MAX_AGGS] = {};
@@ -2212,6 +2235,9 @@ nut_status nut_eval_rows(nut_ctx *c, const nut_agg_spec *s, const int64_t *rows,
   if (!rows && m > s->n) return fail(NUT_ERR_INVALID_ARG, "nut_eval_rows: m > s->n without row ids");
   for (int i = 0; i < s->nprog_cols; ++i)
     if (!s->prog_col[i]) return fail(NUT_ERR_INVALID_ARG, "nut_eval_rows: NULL program column");
+  for (int i = 0; i < s->nprog_cols; ++i)
+    if (type_known(s->prog_col_type[i]) && !type_aligned(s->prog_col[i], s->prog_col_type[i]))
+      return fail(NUT_ERR_INVALID_ARG, "nut_eval_rows: program column " + std::to_string(i) + " is not aligned to its type");
   for (int a = 0; a < s->naggs; ++a)
     if (!out[a]) return fail(NUT_ERR_INVALID_ARG, "nut_eval_rows: NULL output column");
   DeviceGuard dg(c->device);

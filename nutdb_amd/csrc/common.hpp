@@ -114,6 +114,72 @@ __device__ __forceinline__ bool cmp_f64(double v, int op, double k) {
 typedef int64_t i64x2 __attribute__((ext_vector_type(2)));
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
+// ---------------------------------------------------------------- physical column types
+// A narrow column (nut_type NUT_T_I32 .. NUT_T_F32) is read at its stored width and widened
+// into the 8-byte word every consumer computes on: sign / zero extension, F32 -> f64 bits.
+__host__ __device__ constexpr bool type_known(int t) { return t == NUT_T_I64 || t == NUT_T_F64 || (t >= NUT_T_I32 && t <= NUT_T_F32); }
+__host__ __device__ constexpr int type_width(int t) {
+  return (t == NUT_T_I32 || t == NUT_T_U32 || t == NUT_T_F32) ? 4
+         : (t == NUT_T_I16 || t == NUT_T_U16) ? 2
+         : (t == NUT_T_I8 || t == NUT_T_U8) ? 1 : 8;
+}
+__host__ __device__ constexpr bool type_is_float(int t) { return t == NUT_T_F64 || t == NUT_T_F32; }
+#ifndef __HIPCC_RTC__
+// (host) a column of type t may start at p: aligned to its width
+inline bool type_aligned(const void *p, int t) { return ((uintptr_t)p & (uintptr_t)(type_width(t) - 1)) == 0; }
+#endif
+
+// `raw`: the stored bytes of one value of a narrow type T, zero-extended
+template <int T>
+__device__ __forceinline__ uint64_t widen_raw(uint32_t raw) {
+  if constexpr (T == NUT_T_I32) return (uint64_t)(int64_t)(int32_t)raw;
+  else if constexpr (T == NUT_T_I16) return (uint64_t)(int64_t)(short)raw;
+  else if constexpr (T == NUT_T_I8) return (uint64_t)(int64_t)(signed char)raw;
+  else if constexpr (T == NUT_T_F32) return as_u64((double)__uint_as_float(raw));
+  else return (uint64_t)raw;
+}
+// the widened word of row r of a column of type T (NT: non-temporal, a streamed column)
+template <int T, bool NT>
+__device__ __forceinline__ uint64_t load_word(const void *col, uint64_t r) {
+  constexpr int W = type_width(T);
+  if constexpr (W == 8) {
+    const uint64_t *q = (const uint64_t *)col + r;
+    return NT ? __builtin_nontemporal_load(q) : *q;
+  } else if constexpr (W == 4) {
+    const uint32_t *q = (const uint32_t *)col + r;
+    return widen_raw<T>(NT ? __builtin_nontemporal_load(q) : *q);
+  } else if constexpr (W == 2) {
+    const uint16_t *q = (const uint16_t *)col + r;
+    return widen_raw<T>(NT ? __builtin_nontemporal_load(q) : *q);
+  } else {
+    const uint8_t *q = (const uint8_t *)col + r;
+    return widen_raw<T>(NT ? __builtin_nontemporal_load(q) : *q);
+  }
+}
+// rows i, i + 1 (i even) of a column whose base is aligned to 2 x its width: one
+// non-temporal load of both values
+template <int T>
+__device__ __forceinline__ void load_pair(const void *col, uint64_t i, uint64_t &x, uint64_t &y) {
+  constexpr int W = type_width(T);
+  if constexpr (W == 8) {
+    const u64x2 v = __builtin_nontemporal_load(reinterpret_cast<const u64x2 *>((const uint64_t *)col + i));
+    x = v.x;
+    y = v.y;
+  } else if constexpr (W == 4) {
+    const uint64_t v = __builtin_nontemporal_load(reinterpret_cast<const uint64_t *>((const uint32_t *)col + i));
+    x = widen_raw<T>((uint32_t)v);
+    y = widen_raw<T>((uint32_t)(v >> 32));
+  } else if constexpr (W == 2) {
+    const uint32_t v = __builtin_nontemporal_load(reinterpret_cast<const uint32_t *>((const uint16_t *)col + i));
+    x = widen_raw<T>(v & 0xFFFFu);
+    y = widen_raw<T>(v >> 16);
+  } else {
+    const uint32_t v = __builtin_nontemporal_load(reinterpret_cast<const uint16_t *>((const uint8_t *)col + i));
+    x = widen_raw<T>(v & 0xFFu);
+    y = widen_raw<T>(v >> 8);
+  }
+}
+
 #ifndef __HIPCC_RTC__
 // ---------------------------------------------------------------- host side
 void set_error(const std::string &msg);

@@ -85,7 +85,8 @@ struct Gen {
       switch (op) {
         case NUT_P_COL:
           if (nd.arg < 0 || nd.arg >= ncols) return fail("program column index out of range");
-          if (col_types[nd.arg] == NUT_T_F64) r = {NUT_PT_F64, "as_f64(v[" + std::to_string(nd.arg) + "][r])"};
+          // (a narrow column reaches the program widened: v[c][r] is always the 8-byte word)
+          if (type_is_float(col_types[nd.arg])) r = {NUT_PT_F64, "as_f64(v[" + std::to_string(nd.arg) + "][r])"};
           else r = {NUT_PT_I64, "((int64_t)v[" + std::to_string(nd.arg) + "][r])"};
           break;
         case NUT_P_I64: r = {NUT_PT_I64, "((int64_t)" + konst((uint64_t)nd.v) + ")"}; break;
@@ -367,11 +368,20 @@ nut_status jit_shape(const nut_agg_spec *s, const int32_t *kinds, JitShape &out)
   }
   uint32_t kp = 0;
   for (int a = 0; a < s->naggs; ++a) kp |= (uint32_t)(kinds[a] & 15) << (4 * a);
+  // physical column types (nut_type, 4 bits each): part of the source, so of the cache key
+  uint64_t ct = 0;
+  for (int c = 0; c < s->nprog_cols && c < NUT_MAX_PROG_COLS; ++c) {
+    if (!type_known(s->prog_col_type[c]))
+      return fail(NUT_ERR_INVALID_ARG, "expression program column " + std::to_string(c) + " has unknown type " +
+                                           std::to_string(s->prog_col_type[c]) + " (int64, float64 or a narrow nut_type)");
+    ct |= (uint64_t)s->prog_col_type[c] << (4 * c);
+  }
   const int ma = s->naggs > 0 ? s->naggs : 1;
   std::string src;
   src += "struct QShape {\n";
   src += "  static constexpr bool kProg = true;\n";
   src += "  static constexpr int MP = 0, MV = " + std::to_string(s->nprog_cols) + ", MA = " + std::to_string(ma) + ";\n";
+  src += "  static constexpr uint64_t kColTypes = " + std::to_string(ct) + "ull;\n";
   src += "  static constexpr uint32_t kKinds = " + std::to_string(kp) + "u;\n";
   src += "  static constexpr int kKeyProg = " + std::to_string(kmask) + ";\n";
   src += "  __device__ static constexpr int np(const AggArgs &) { return 0; }\n";

@@ -476,6 +476,17 @@ __global__ void gather_u64_kernel(const uint64_t *__restrict__ src, const int64_
   }
 }
 
+// the typed sibling (nut_gather_typed): src holds values of physical type T (common.hpp),
+// out their widened 8-byte words; idx NULL = rows 0..n-1 (a pure widening pass)
+template <int T>
+__global__ void gather_typed_kernel(const void *__restrict__ src, const int64_t *idx, uint64_t n,
+                                    uint64_t null_bits, uint64_t *out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const int64_t j = idx ? idx[i] : (int64_t)i;
+    out[i] = j < 0 ? null_bits : load_word<T, false>(src, (uint64_t)j);
+  }
+}
+
 }  // namespace nut
 
 using namespace nut;
@@ -814,6 +825,35 @@ nut_status nut_gather_u64(nut_ctx *c, const uint64_t *src, const int64_t *idx, u
   DeviceGuard dg(c->device);
   const unsigned g = (unsigned)std::min<uint64_t>((n + 255) / 256, c->num_cus * 16ull);
   hipLaunchKernelGGL(gather_u64_kernel, dim3(g), dim3(256), 0, c->stream, src, idx, n, null_bits, out);
+  NUT_HIP(hipGetLastError());
+  return NUT_OK;
+}
+
+nut_status nut_gather_typed(nut_ctx *c, const void *src, int src_type, const int64_t *idx, uint64_t n,
+                            uint64_t null_bits, uint64_t *out) {
+  if (!c || (n && !out)) return fail(NUT_ERR_INVALID_ARG, "nut_gather_typed: NULL argument");
+  if (!type_known(src_type)) return fail(NUT_ERR_INVALID_ARG, "nut_gather_typed: unknown column type " + std::to_string(src_type));
+  if (n == 0) return NUT_OK;
+  if (!src && !idx) return fail(NUT_ERR_INVALID_ARG, "nut_gather_typed: NULL source column");
+  if (!type_aligned(src, src_type))
+    return fail(NUT_ERR_INVALID_ARG, "nut_gather_typed: source column is not aligned to its type");
+  if (type_width(src_type) == 8 && idx) return nut_gather_u64(c, (const uint64_t *)src, idx, n, null_bits, out);
+  DeviceGuard dg(c->device);
+  const unsigned g = (unsigned)std::min<uint64_t>((n + 255) / 256, c->num_cus * 16ull);
+  auto launch = [&](auto TC) {
+    hipLaunchKernelGGL(gather_typed_kernel<decltype(TC)::value>, dim3(g), dim3(256), 0, c->stream, src, idx, n,
+                       null_bits, out);
+  };
+  switch (src_type) {
+    case NUT_T_I32: launch(std::integral_constant<int, NUT_T_I32>{}); break;
+    case NUT_T_I16: launch(std::integral_constant<int, NUT_T_I16>{}); break;
+    case NUT_T_I8: launch(std::integral_constant<int, NUT_T_I8>{}); break;
+    case NUT_T_U32: launch(std::integral_constant<int, NUT_T_U32>{}); break;
+    case NUT_T_U16: launch(std::integral_constant<int, NUT_T_U16>{}); break;
+    case NUT_T_U8: launch(std::integral_constant<int, NUT_T_U8>{}); break;
+    case NUT_T_F32: launch(std::integral_constant<int, NUT_T_F32>{}); break;
+    default: launch(std::integral_constant<int, NUT_T_I64>{}); break;  // 8-byte words, idx NULL: a copy
+  }
   NUT_HIP(hipGetLastError());
   return NUT_OK;
 }

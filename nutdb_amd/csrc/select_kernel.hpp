@@ -49,8 +49,12 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(SelArgs sa) {
       const uint64_t r = base + (uint64_t)i * SEL_THREADS;
       const bool ok = r < n;
       uint64_t vv[S::MV > 0 ? S::MV : 1][1];
+      if constexpr (shape_narrow<S>()) {  // columns at their stored width, widened
+        load_row_typed<S, true>(sa.a.val_col, r, ok, vv);
+      } else {
 #pragma unroll
-      for (int c = 0; c < S::MV; ++c) vv[c][0] = ok ? __builtin_nontemporal_load(sa.a.val_col[c] + r) : 0;
+        for (int c = 0; c < S::MV; ++c) vv[c][0] = ok ? __builtin_nontemporal_load(sa.a.val_col[c] + r) : 0;
+      }
       bool e = false;
       const bool w = S::where(sa.a, vv, 0, e) && ok;
       err = err || (e && ok);
@@ -135,8 +139,12 @@ __global__ __launch_bounds__(EV_THREADS) void eval_kernel(EvalArgs ea) {
   for (uint64_t i = (uint64_t)blockIdx.x * EV_THREADS + threadIdx.x; i < ea.m; i += stride) {
     const uint64_t r = ea.rows ? (uint64_t)ea.rows[i] : i;
     uint64_t vv[S::MV > 0 ? S::MV : 1][1];
+    if constexpr (shape_narrow<S>()) {
+      load_row_typed<S, false>(ea.a.val_col, r, true, vv);
+    } else {
 #pragma unroll
-    for (int c = 0; c < S::MV; ++c) vv[c][0] = ea.a.val_col[c][r];
+      for (int c = 0; c < S::MV; ++c) vv[c][0] = ea.a.val_col[c][r];
+    }
 #pragma unroll
     for (int a = 0; a < S::MA; ++a) {
       if (a >= ea.nout) break;

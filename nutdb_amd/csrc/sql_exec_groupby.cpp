@@ -502,8 +502,81 @@ nut_status groupby_bound(nut_ctx *c, const nut_plan &p, const nut_column *const 
 // key fields and the key-tuple order are the int64 ones, and the outputs decode the words
 // back (+0.0 for the zeros, the quiet +NaN for the NaNs).  A WHERE or aggregate over the
 // same column still reads its float64 values.
-nut_status exec_groupby(nut_ctx *c, const nut_plan &p, const nut_column *const *bound, const Dict *const *dicts,
+bool narrow_groupby_plan(const nut_plan &p, const nut_column *const *bound, nut_plan &q) {
+  bool any = false;
+  for (size_t i = 0; i < p.cols.size(); ++i) any = any || col_narrow(bound[i]);
+  if (!any) return false;
+  q = p;
+  auto col_prog = [](int ci) {
+    PNode nd;
+    nd.op = NUT_P_COL;
+    nd.col = ci;
+    return PProg{nd};
+  };
+  if (!q.compiled) {
+    std::vector<PProg> cs;
+    for (const PlanPred &pr : q.preds) cs.push_back(pred_prog(pr));
+    q.preds.clear();
+    q.where = and_all(cs);
+    for (PlanAgg &a : q.aggs) {
+      if (a.op == NUT_AGG_COUNT) continue;
+      // the fused expressions (agg_ops.hpp eval<>), same operations in the same order
+      auto v = [&](int j) { return col_prog(q.vals[a.arg[j]]); };
+      PProg e = v(0);
+      if (a.expr == NUT_EX_MUL || a.expr == NUT_EX_ADD || a.expr == NUT_EX_SUB) {
+        append(e, v(1));
+        emit(e, a.expr == NUT_EX_MUL ? NUT_P_MUL : a.expr == NUT_EX_ADD ? NUT_P_ADD : NUT_P_SUB);
+      } else if (a.expr == NUT_EX_MUL_1M || a.expr == NUT_EX_MUL_1M_1P) {
+        emit_int(e, 1);
+        append(e, v(1));
+        emit(e, NUT_P_SUB);
+        emit(e, NUT_P_MUL);
+        if (a.expr == NUT_EX_MUL_1M_1P) {
+          emit_int(e, 1);
+          append(e, v(2));
+          emit(e, NUT_P_ADD);
+          emit(e, NUT_P_MUL);
+        }
+      }
+      a.val = std::move(e);
+    }
+    q.compiled = true;
+  }
+  if (q.key_progs.size() != q.keys.size()) {
+    q.key_progs.clear();
+    q.key_text.clear();
+    for (int k : q.keys) {
+      q.key_progs.push_back(k >= 0 ? col_prog(k) : PProg{});
+      q.key_text.push_back(k >= 0 ? q.cols[k] : std::string());
+    }
+  }
+  // a narrow integer key is a computed key: its one-node program, evaluated in the kernel
+  for (size_t j = 0; j < q.keys.size(); ++j)
+    if (q.keys[j] >= 0 && col_narrow(bound[q.keys[j]]) && !type_is_float(bound[q.keys[j]]->type)) q.keys[j] = -1;
+  return true;
+}
+
+nut_status exec_groupby(nut_ctx *c, const nut_plan &p0, const nut_column *const *bound0, const Dict *const *dicts,
                         uint64_t n, uint64_t hint, nut_result *r) {
+  // narrow columns: the plan in expression mode; a Float32 key column widened (the float64
+  // key words below need the whole 8-byte column)
+  nut_plan nq;
+  const bool narrow = narrow_groupby_plan(p0, bound0, nq);
+  const nut_plan &p = narrow ? nq : p0;
+  std::vector<const nut_column *> nb(bound0, bound0 + p0.cols.size());
+  std::deque<DevBuf> wide;
+  std::deque<nut_column> widec;
+  for (size_t j = 0; narrow && j < p.keys.size(); ++j) {
+    const int k = p.keys[j];
+    if (k < 0 || !col_narrow(nb[k])) continue;  // (narrow and still a plain key: Float32)
+    wide.emplace_back();
+    if (wide.back().alloc(c, std::max<uint64_t>(n, 1) * 8) != hipSuccess) return fail(NUT_ERR_OOM, "hipMalloc (Float32 key)");
+    nut_status st = nut_gather_typed(c, nb[k]->data, nb[k]->type, nullptr, n, 0, (uint64_t *)wide.back().p);
+    if (st) return st;
+    widec.push_back(nut_column{nb[k]->name, wide.back().p, NUT_T_F64});
+    nb[k] = &widec.back();
+  }
+  const nut_column *const *bound = nb.data();
   std::vector<char> fkey(p.keys.size(), 0);
   bool any = false;
   for (size_t j = 0; j < p.keys.size(); ++j)

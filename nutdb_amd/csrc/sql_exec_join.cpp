@@ -177,6 +177,15 @@ const nut_plan *expand_star(const nut_plan &p, const std::vector<std::string> &n
 nut_status exec_join(nut_ctx *c, const nut_plan &p, const nut_column *lc, int nl, uint64_t lrows,
                      const nut_column *rc, int nr, uint64_t rrows, uint64_t hint, nut_result *r,
                      const Dict *const *ldict, const Dict *const *rdict) {
+  {  // narrow columns: the join, its gathers and the plan over the joined rows take 8-byte words
+    std::vector<nut_column> wl, wr;
+    std::deque<DevBuf> bufs;
+    const nut_column *l2 = lc, *r2 = rc;
+    nut_status ws = widen_cols(c, lc, nl, lrows, wl, bufs, &l2);
+    if (!ws) ws = widen_cols(c, rc, nr, rrows, wr, bufs, &r2);
+    if (ws) return ws;
+    if (l2 != lc || r2 != rc) return exec_join(c, p, l2, nl, lrows, r2, nr, rrows, hint, r, ldict, rdict);
+  }
   const size_t nc = p.cols.size();
   std::vector<int> side(nc);
   std::vector<const nut_column *> src(nc);
@@ -567,6 +576,18 @@ nut_status residual_semi(nut_ctx *c, const nut_plan &p, int k, int op, const nut
 nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *tabs, const int *ncols,
                       const uint64_t *nrows, int nt, uint64_t hint, nut_result *r,
                       const Dict *const *const *tdicts) {
+  {  // narrow columns: widened up front (exec_join)
+    std::vector<std::vector<nut_column>> w(nt);
+    std::deque<DevBuf> bufs;
+    std::vector<const nut_column *> t2(tabs, tabs + nt);
+    bool any = false;
+    for (int k = 0; k < nt; ++k) {
+      nut_status ws = widen_cols(c, tabs[k], ncols[k], nrows[k], w[k], bufs, &t2[k]);
+      if (ws) return ws;
+      any = any || t2[k] != tabs[k];
+    }
+    if (any) return exec_joinn(c, p, t2.data(), ncols, nrows, nt, hint, r, tdicts);
+  }
   const size_t nc = p.cols.size();
   if (nt != (int)p.jn.size() + 1)
     return fail(NUT_ERR_INVALID_ARG, "nut_plan_executen: the plan joins " + std::to_string(p.jn.size() + 1) +
@@ -986,6 +1007,28 @@ nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *ta
 }
 
 
+nut_status widen_cols(nut_ctx *c, const nut_column *cols, int n, uint64_t rows, std::vector<nut_column> &copy,
+                      std::deque<DevBuf> &bufs, const nut_column **out) {
+  *out = cols;
+  bool any = false;
+  for (int i = 0; i < n; ++i) any = any || col_narrow(&cols[i]);
+  if (!any) return NUT_OK;
+  copy.assign(cols, cols + n);
+  for (nut_column &col : copy) {
+    if (!col_narrow(&col)) continue;
+    const int t = col.type;
+    col.type = logical_type(t);
+    if (!rows || !col.data) continue;
+    bufs.emplace_back();
+    if (bufs.back().alloc(c, rows * 8) != hipSuccess) return fail(NUT_ERR_OOM, "hipMalloc (widened column)");
+    nut_status st = nut_gather_typed(c, col.data, t, nullptr, rows, 0, (uint64_t *)bufs.back().p);
+    if (st) return st;
+    col.data = bufs.back().p;
+  }
+  *out = copy.data();
+  return NUT_OK;
+}
+
 nut_status stage_host(nut_ctx *c, const nut_column *cols, int n, uint64_t rows, HostStage &hs, const nut_column **out) {
   *out = cols;
   bool any = false;
@@ -997,8 +1040,9 @@ nut_status stage_host(nut_ctx *c, const nut_column *cols, int n, uint64_t rows, 
     col.type &= ~NUT_COL_HOST;
     if (!rows || !col.data) continue;
     hs.bufs.emplace_back();
-    NUT_HIP(hs.bufs.back().alloc(c, rows * 8));
-    NUT_HIP(hipMemcpyAsync(hs.bufs.back().p, col.data, rows * 8, hipMemcpyHostToDevice, c->stream));
+    const size_t bytes = rows * (size_t)(type_known(col.type) ? type_width(col.type) : 8);  // the declared width
+    NUT_HIP(hs.bufs.back().alloc(c, bytes));
+    NUT_HIP(hipMemcpyAsync(hs.bufs.back().p, col.data, bytes, hipMemcpyHostToDevice, c->stream));
     col.data = hs.bufs.back().p;
   }
   *out = hs.cols.data();

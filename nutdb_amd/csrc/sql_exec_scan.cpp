@@ -131,7 +131,7 @@ nut_status exec_sort_rows(nut_ctx *c, const nut_plan &p, const nut_column *const
                : -1;
     if (dc >= 0 && dicts && dicts[dc]) sdict[j] = dc;
     r->names.push_back(p.outs[j].name);
-    r->types.push_back(sdict[j] >= 0 ? NUT_T_STR : p.projs[j] >= 0 ? bound[p.projs[j]]->type : ctype[j]);
+    r->types.push_back(sdict[j] >= 0 ? NUT_T_STR : p.projs[j] >= 0 ? logical_type(bound[p.projs[j]]->type) : ctype[j]);
   }
   uint64_t cnt = 0;
   DevBuf rows, perm, keys;
@@ -155,10 +155,10 @@ nut_status exec_sort_rows(nut_ctx *c, const nut_plan &p, const nut_column *const
     // top-k on the most significant key: keep the candidate rows (ascending ids)
     const nut_column *kc = bound[p.sort_keys[0].first];
     NUT_HIP(keys.alloc(c, cnt * 8));
-    nut_status s = nut_gather_u64(c, (const uint64_t *)kc->data, (const int64_t *)rows.p, cnt, 0, (uint64_t *)keys.p);
+    nut_status s = gather_col(c, kc, (const int64_t *)rows.p, cnt, (uint64_t *)keys.p);
     DevBuf pos;
     uint64_t m2 = cnt;
-    if (!s) s = topk_reduce(c, p, keys.p, kc->type, p.sort_keys[0].second, cnt, pos, &m2);
+    if (!s) s = topk_reduce(c, p, keys.p, logical_type(kc->type), p.sort_keys[0].second, cnt, pos, &m2);
     if (s) return s;
     if (m2 < cnt) {
       NUT_HIP(perm.alloc(c, std::max<uint64_t>(m2, 1) * 8));
@@ -184,15 +184,14 @@ nut_status exec_sort_rows(nut_ctx *c, const nut_plan &p, const nut_column *const
     nut_status s = NUT_OK;
     for (size_t i = p.sort_keys.size(); i-- > 0 && !s;) {
       const nut_column *kc = bound[p.sort_keys[i].first];
-      s = nut_gather_u64(c, (const uint64_t *)kc->data, (const int64_t *)rows.p, cnt, 0, (uint64_t *)keys.p);
-      if (!s) s = nut_sort_pairs(c, keys.p, kc->type, p.sort_keys[i].second ? 1 : 0, (const int64_t *)rows.p,
+      s = gather_col(c, kc, (const int64_t *)rows.p, cnt, (uint64_t *)keys.p);
+      if (!s) s = nut_sort_pairs(c, keys.p, logical_type(kc->type), p.sort_keys[i].second ? 1 : 0, (const int64_t *)rows.p,
                                  (int64_t *)perm.p, cnt);
       std::swap(rows.p, perm.p);  // the sorted row ids feed the next (more significant) key
     }
     for (size_t j = 0; j < np && !s; ++j)
       if (!computed_proj(p, j))
-        s = nut_gather_u64(c, (const uint64_t *)bound[p.projs[j]]->data, (const int64_t *)rows.p, cnt, 0,
-                           (uint64_t *)r->dev + j * cnt);
+        s = gather_col(c, bound[p.projs[j]], (const int64_t *)rows.p, cnt, (uint64_t *)r->dev + j * cnt);
     for (size_t g = 0; g < specs.size() && !s; ++g) {
       uint64_t *outs[NUT_MAX_AGGS] = {};
       uint8_t *vals[NUT_MAX_AGGS] = {};
@@ -247,16 +246,19 @@ nut_status scan_route(const nut_plan &p, const nut_column *const *bound, const D
       if (dicts && dicts[k.first])
         return fail(NUT_ERR_PLAN, "ORDER BY string column '" + p.cols[k.first] + "' is not executed (dictionary codes "
                                   "are in first-seen order)");
-      if (bound[k.first]->type != NUT_T_I64 && bound[k.first]->type != NUT_T_F64)
+      if (!type_known(bound[k.first]->type))
         return fail(NUT_ERR_PLAN, "ORDER BY column '" + p.cols[k.first] + "' must be int64 or float64");
     }
     *route = S_ROWID;
     return NUT_OK;
   }
-  bool f64 = false;
-  for (int pj : p.projs) f64 = f64 || bound[pj]->type == NUT_T_F64;
-  for (const PlanPred &pr : p.preds) f64 = f64 || bound[pr.col]->type == NUT_T_F64;
-  if (!p.compiled && (f64 || (p.kind == NUT_PLAN_FILTER && dicts && dicts[p.proj]))) {
+  // (a narrow column of any type reruns too: only the generated scan kernel and the typed
+  // gather read narrow bytes, never the fused filter / sort)
+  bool f64 = false, narrow = false;
+  for (int pj : p.projs) f64 = f64 || type_is_float(bound[pj]->type), narrow = narrow || col_narrow(bound[pj]);
+  for (const PlanPred &pr : p.preds)
+    f64 = f64 || type_is_float(bound[pr.col]->type), narrow = narrow || col_narrow(bound[pr.col]);
+  if (!p.compiled && (f64 || narrow || (p.kind == NUT_PLAN_FILTER && dicts && dicts[p.proj]))) {
     *route = S_RERUN_EXPR;
     return NUT_OK;
   }
@@ -267,7 +269,7 @@ nut_status scan_route(const nut_plan &p, const nut_column *const *bound, const D
   for (const PlanPred &pr : p.preds)
     if (pr.c.is_str) return fail(NUT_ERR_PLAN, "string constant " + cval_str(pr.c) + " compared with an int64 column");
   for (int pj : p.projs)
-    if (bound[pj]->type != NUT_T_I64 && !(p.compiled && bound[pj]->type == NUT_T_F64))
+    if (!type_known(bound[pj]->type) || (logical_type(bound[pj]->type) != NUT_T_I64 && !p.compiled))
       return fail(NUT_ERR_PLAN, "column '" + p.cols[pj] + "' must be int64 or float64 for this scan/sort");
   if (p.compiled)
     *route = p.kind == NUT_PLAN_FILTER ? S_EXPR_FILTER : f64 ? S_EXPR_SORT_F64 : S_EXPR_SORT;
@@ -300,7 +302,7 @@ nut_status exec_scan(nut_ctx *c, const nut_plan &p, const nut_column *const *bou
   const nut_column *col = bound[p.proj];
   for (size_t j = 0; j < p.projs.size(); ++j) {
     r->names.push_back(p.outs[j].name);
-    r->types.push_back(dicts && dicts[p.projs[j]] ? NUT_T_STR : bound[p.projs[j]]->type);
+    r->types.push_back(dicts && dicts[p.projs[j]] ? NUT_T_STR : logical_type(bound[p.projs[j]]->type));
   }
   int op = NUT_GE;
   int64_t k = INT64_MIN;  // no predicate: every row passes
@@ -331,12 +333,11 @@ nut_status exec_scan(nut_ctx *c, const nut_plan &p, const nut_column *const *bou
     if (p.kind == NUT_PLAN_FILTER) {
       r->dev_stride = cnt;
       for (size_t j = 0; j < k && !s; ++j)
-        s = nut_gather_u64(c, (const uint64_t *)bound[p.projs[j]]->data, (const int64_t *)rows.p, cnt, 0,
-                           (uint64_t *)r->dev + j * cnt);
+        s = gather_col(c, bound[p.projs[j]], (const int64_t *)rows.p, cnt, (uint64_t *)r->dev + j * cnt);
     } else {
       DevBuf vals, pos, cv;
       NUT_HIP(vals.alloc(c, std::max<uint64_t>(cnt, 1) * 8));
-      s = nut_gather_u64(c, (const uint64_t *)col->data, (const int64_t *)rows.p, cnt, 0, (uint64_t *)vals.p);
+      s = gather_col(c, col, (const int64_t *)rows.p, cnt, (uint64_t *)vals.p);
       // float64: the words sort (and top-k select) as int64 in the IEEE total order, and
       // map back after the sort (-0.0 before +0.0, NaNs at the ends by sign)
       const bool fo = route == S_EXPR_SORT_F64;

@@ -325,7 +325,7 @@ nut_status nut_plan_route(const nut_plan *p, const nut_column *cols, int ncols, 
   for (size_t i = 0; i < p->cols.size(); ++i) {
     bound[i] = bind(*p, (int)i, cols, ncols);
     if (!bound[i]) return fail(NUT_ERR_INVALID_ARG, "nut_plan_route: column '" + p->cols[i] + "' is not bound");
-    if (bound[i]->type != NUT_T_I64 && bound[i]->type != NUT_T_F64)
+    if (!type_known(bound[i]->type))
       return fail(NUT_ERR_INVALID_ARG, "nut_plan_route: column '" + p->cols[i] + "' has an unknown type");
   }
   std::string route;
@@ -334,11 +334,13 @@ nut_status nut_plan_route(const nut_plan *p, const nut_column *cols, int ncols, 
     ProgStore store;
     std::vector<int> agg_f64;
     GbExtra gx;
-    // float64 key columns are grouped on int64 key words (exec_groupby)
+    nut_plan nq;  // narrow columns: the expression-mode plan exec_groupby runs
+    if (narrow_groupby_plan(*p, bound.data(), nq)) p = &nq;
+    // float64 key columns (a Float32 one: widened first) are grouped on int64 key words (exec_groupby)
     std::deque<nut_column> words;
     int nf = 0;
     for (int k : p->keys)
-      if (k >= 0 && bound[k]->type == NUT_T_F64) {
+      if (k >= 0 && type_is_float(bound[k]->type)) {
         words.push_back(nut_column{bound[k]->name, nullptr, NUT_T_I64});
         bound[k] = &words.back();
         ++nf;
@@ -417,7 +419,7 @@ nut_status nut_plan_execute(nut_ctx *c, const nut_plan *p, const nut_column *col
   for (size_t i = 0; i < p->cols.size(); ++i) {
     bound[i] = bind(*p, (int)i, cols, ncols);
     if (!bound[i]) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: column '" + p->cols[i] + "' is not bound");
-    if (bound[i]->type != NUT_T_I64 && bound[i]->type != NUT_T_F64)
+    if (!type_known(bound[i]->type))
       return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: column '" + p->cols[i] + "' has an unknown type");
     if (nrows && !bound[i]->data) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: column '" + p->cols[i] + "' is NULL");
   }
@@ -567,7 +569,12 @@ nut_status nut_plan_prepare(const nut_plan *p, const nut_column *cols, int ncols
     }
   }
   if (!p->uni.empty()) return NUT_OK;
-  if (!p->compiled) return NUT_OK;  // precompiled kernels only
+  bool any_narrow = false;
+  for (int i = 0; i < ncols; ++i) {
+    const int t = cols[i].type & ~NUT_COL_HOST;
+    any_narrow = any_narrow || (type_known(t) && type_width(t) < 8);
+  }
+  if (!p->compiled && !(any_narrow && p->kind == NUT_PLAN_GROUPBY)) return NUT_OK;  // precompiled kernels only
   // scalar subqueries: their values (int64 or f64 constants) decide the program types, so
   // the shape is compiled when the plan executes with the values in place
   if (!p->subs.empty()) return NUT_OK;
@@ -586,8 +593,14 @@ nut_status nut_plan_prepare(const nut_plan *p, const nut_column *cols, int ncols
     typed[i] = *bound[i];
     typed[i].type &= ~NUT_COL_HOST;  // only the type matters here
     bound[i] = &typed[i];
-    if (bound[i]->type != NUT_T_I64 && bound[i]->type != NUT_T_F64)
+    if (!type_known(bound[i]->type))
       return fail(NUT_ERR_INVALID_ARG, "nut_plan_prepare: column '" + p->cols[i] + "' has an unknown type");
+  }
+  nut_plan nq;  // narrow columns: the expression-mode plan that executes (a Float32 key is widened there)
+  if (p->kind == NUT_PLAN_GROUPBY && narrow_groupby_plan(*p, bound.data(), nq)) {
+    for (int k : nq.keys)  // (a Float32 key groups on key words made at execution: compiled then)
+      if (k >= 0 && col_narrow(&typed[k])) return NUT_OK;
+    p = &nq;
   }
   nut_agg_spec s;
   ProgStore store;

@@ -268,6 +268,28 @@ struct HostStage {
 nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const Dict *const *dicts, uint64_t n,
                       nut_agg_spec &s, ProgStore &store, std::vector<int> &agg_f64, GbExtra *gx = nullptr);
 
+// ---- narrow bound columns (nut_type NUT_T_I32 .. NUT_T_F32).  One rule:
+// only the generated kernels (through build_spec's program columns) and nut_gather_typed
+// read narrow bytes; every other consumer gets 8-byte words.
+// the type a column computes as and results report: int64 / float64 (strings stay)
+inline int logical_type(int t) { return t == NUT_T_STR ? t : type_is_float(t) ? NUT_T_F64 : NUT_T_I64; }
+inline bool col_narrow(const nut_column *c) { return type_known(c->type) && type_width(c->type) < 8; }
+// out[i] = the 8-byte word of col[idx[i]]: carries a bound column of any type through row ids
+inline nut_status gather_col(nut_ctx *c, const nut_column *col, const int64_t *idx, uint64_t n, uint64_t *out) {
+  return nut_gather_typed(c, col->data, col->type, idx, n, 0, out);
+}
+// cols with every narrow column replaced by a widened temporary (nut_gather_typed, idx =
+// NULL; freed with `bufs`): for consumers that need whole 8-byte columns (joins).  *out =
+// cols itself when none is narrow.
+nut_status widen_cols(nut_ctx *c, const nut_column *cols, int n, uint64_t rows, std::vector<nut_column> &copy,
+                      std::deque<DevBuf> &bufs, const nut_column **out);
+// A GROUPBY plan over bound columns some of which are narrow, as the plan the generated
+// kernels run (false: none is narrow, q untouched): a fused plan becomes an expression-mode
+// one (predicates -> the WHERE program, fused expressions -> value programs) and narrow
+// integer keys become one-node key programs (the packed-key path).  Float32 keys are left
+// to the caller (exec_groupby widens them for the float64 key words).
+bool narrow_groupby_plan(const nut_plan &p, const nut_column *const *bound, nut_plan &q);
+
 // A plan column name inside EXISTS / IN subquery `scope` (>= 1): "\x1f<scope>\x1f<name>",
 // so the same name in the outer query and in a subquery are two plan columns.
 std::string scoped_name(int scope, sv name);

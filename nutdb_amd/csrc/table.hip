@@ -114,9 +114,9 @@ nut_status grow(nut_ctx *c, TCol &col, uint64_t need) {
   uint64_t cap = col.cap ? col.cap : 1024;
   while (cap < need) cap *= 2;
   void *p = nullptr;
-  NUT_HIP(hipMalloc(&p, cap * 8));
+  NUT_HIP(hipMalloc(&p, cap * (size_t)col.esize));
   if (col.n) {
-    hipError_t e = hipMemcpyAsync(p, col.dev, col.n * 8, hipMemcpyDeviceToDevice, c->stream);
+    hipError_t e = hipMemcpyAsync(p, col.dev, col.n * (size_t)col.esize, hipMemcpyDeviceToDevice, c->stream);
     if (e != hipSuccess) {
       (void)hipFree(p);
       return hip_fail(e, "nut_table_append: grow");
@@ -219,6 +219,11 @@ nut_status nut_table_append(nut_ctx *c, nut_table *t, int j, const void *data, c
   } else if (col.width == 8 && col.kind != NUT_COL_UINT) {
     NUT_HIP(hipMemcpyAsync(dst, data, n * 8, hipMemcpyHostToDevice, c->stream));
     NUT_HIP(hipStreamSynchronize(c->stream));
+  } else if (col.esize < 8) {
+    // a narrow table: the declared width straight into HBM, no widening pass
+    NUT_HIP(hipMemcpyAsync((uint8_t *)col.dev + col.n * (size_t)col.esize, data, n * (size_t)col.esize,
+                           hipMemcpyHostToDevice, c->stream));
+    NUT_HIP(hipStreamSynchronize(c->stream));
   } else {
     // narrow bytes over PCIe, widened in HBM (staged through ctx scratch in chunks)
     const uint64_t chunk = (64ull << 20) / (uint64_t)col.width;
@@ -243,6 +248,28 @@ nut_status nut_table_append(nut_ctx *c, nut_table *t, int j, const void *data, c
     if (flag) return fail(NUT_ERR_UNSUPPORTED, "column '" + col.name + "': UInt64 values >= 2^63 are not executed");
   }
   col.n += n;
+  return NUT_OK;
+}
+
+nut_status nut_table_set_narrow(nut_table *t, int on) {
+  if (!t) return fail(NUT_ERR_INVALID_ARG, "nut_table_set_narrow: NULL table");
+  for (const auto &c : t->cols)
+    if (c.n || c.dev) return fail(NUT_ERR_INVALID_ARG, "nut_table_set_narrow: table '" + t->name + "' already has rows");
+  t->narrow = on != 0;
+  for (auto &c : t->cols) {
+    const bool num = c.kind == NUT_COL_INT || c.kind == NUT_COL_UINT || c.kind == NUT_COL_FLOAT || c.kind == NUT_COL_BOOL;
+    if (!num || c.width >= 8 || c.width <= 0) continue;
+    c.esize = t->narrow ? c.width : 8;
+    if (!t->narrow) {
+      c.exec_type = c.kind == NUT_COL_FLOAT ? NUT_T_F64 : NUT_T_I64;
+    } else if (c.kind == NUT_COL_FLOAT) {
+      c.exec_type = NUT_T_F32;
+    } else if (c.kind == NUT_COL_INT) {
+      c.exec_type = c.width == 4 ? NUT_T_I32 : c.width == 2 ? NUT_T_I16 : NUT_T_I8;
+    } else {  // UInt, and Boolean as UInt8
+      c.exec_type = c.width == 4 ? NUT_T_U32 : c.width == 2 ? NUT_T_U16 : NUT_T_U8;
+    }
+  }
   return NUT_OK;
 }
 

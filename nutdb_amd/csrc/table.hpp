@@ -88,7 +88,8 @@ struct TCol {
   int exec_type = NUT_T_I64;
   Dict *dict = nullptr;    // STRING: the table's shared dictionary; ENUM: own
   Dict own;                // ENUM
-  void *dev = nullptr;     // HBM column, 8 B per row
+  void *dev = nullptr;     // HBM column, esize bytes per row
+  int esize = 8;           // 8, or the declared width in a narrow table (nut_table_set_narrow)
   uint64_t n = 0, cap = 0;
 };
 
@@ -99,6 +100,7 @@ struct nut_table {
   std::vector<nut::TCol> cols;
   nut::Dict strings;  // shared by every string-like column
   int device = -1;    // device of the columns (set by the first append)
+  bool narrow = false;  // Int8/16/32, UInt8/16/32, Float32, Boolean columns keep their declared width in HBM
   uint64_t rows() const {
     if (cols.empty()) return 0;
     uint64_t n = cols[0].n;

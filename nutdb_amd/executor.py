@@ -35,6 +35,21 @@ def _dtype_code(t: torch.Tensor) -> int:
     raise TypeError(f"nutexec columns are int64 or float64, got {t.dtype}")
 
 
+# narrow torch dtypes -> physical nut_type codes (uint16 / uint32 where this torch has them)
+_NARROW = {torch.int32: L.T_I32, torch.int16: L.T_I16, torch.int8: L.T_I8, torch.uint8: L.T_U8,
+           torch.float32: L.T_F32}
+for _name, _code in (("uint16", L.T_U16), ("uint32", L.T_U32)):
+    if hasattr(torch, _name):
+        _NARROW[getattr(torch, _name)] = _code
+
+
+def _phys_code(t) -> int:
+    """nut_type of a column the generated kernels and gather read at its stored width:
+    int64 / float64 as _dtype_code, narrow dtypes as their physical code."""
+    code = _NARROW.get(t.dtype)
+    return _dtype_code(t) if code is None else code
+
+
 def _col(t: torch.Tensor, dev: torch.device) -> int:
     if t.device != dev:
         raise ValueError(f"column on {t.device}, executor on {dev}")
@@ -173,7 +188,13 @@ class ProgQuery:
     aggregate argument are RPN programs over `cols`, compiled for the query at run time
     (csrc/jit.cpp).  aggs = [(op, value program or None, mask program or None)]: the
     mask keeps only rows where it is true (CASE without ELSE).  A key is an int64 column
-    or an int64 / bool program over `cols` (a computed key: nut_agg_spec.key_prog)."""
+    or an int64 / bool program over `cols` (a computed key: nut_agg_spec.key_prog).
+    `cols` may be narrow (int8 / 16 / 32, uint8 / 16 / 32, float32): the kernel reads them at
+    their stored width and computes on int64 / float64; a narrow key is the program
+    [("col", c)].  Narrow columns save HBM, not yet time: measured at 1e9 rows (DESIGN.md
+    4.2d) int32 / float32 columns run up to 1.12x faster than widened ones, int8 / int16
+    columns slower (a Q1 with two int8 keys 1.3x) until the kernel holds more rows per lane
+    for them; widen those first (Executor.gather(col, None)) where time matters more."""
     keys: list
     cols: list
     aggs: list
@@ -205,7 +226,7 @@ class ProgQuery:
             if c.numel() != n:
                 raise ValueError("ragged columns")
             s.prog_col[i] = _col(c, dev)
-            s.prog_col_type[i] = _dtype_code(c)
+            s.prog_col_type[i] = _phys_code(c)
         s.where = _prog(self.where, keep)
         if len(self.aggs) > L.NUT_MAX_AGGS:
             raise ValueError("too many aggregates")
@@ -217,7 +238,7 @@ class ProgQuery:
         return s
 
     def result_types(self) -> list:
-        types = (C.c_int32 * max(len(self.cols), 1))(*[_dtype_code(c) for c in self.cols])
+        types = (C.c_int32 * max(len(self.cols), 1))(*[_phys_code(c) for c in self.cols])
         out = []
         for op, val, _ in self.aggs:
             if (AGG[op] if isinstance(op, str) else int(op)) == L.AGG_COUNT:
@@ -591,7 +612,13 @@ class Executor:
         return pi, bi
 
     def gather(self, col: torch.Tensor, idx: torch.Tensor, null=0) -> torch.Tensor:
-        """col[idx] for an int64 / float64 column, `null` where idx < 0 (nut_gather_u64)."""
+        """col[idx] for an int64 / float64 column, `null` where idx < 0 (nut_gather_u64).  A
+        narrow column (int8 / 16 / 32, uint8 / 16 / 32, float32) comes back widened to int64 /
+        float64 (nut_gather_typed); idx None: every row, a pure widening pass."""
+        if col.dtype in _NARROW:
+            return self._gather_typed(col, idx, null)
+        if idx is None:
+            raise TypeError("gather without an index widens a narrow column")
         if col.element_size() != 8 or idx.dtype != torch.int64:
             raise TypeError("gather takes an 8-byte column and an int64 index")
         n = idx.numel()
@@ -602,6 +629,38 @@ class Executor:
                                  C.c_void_p(idx.data_ptr() if n else None), n, nb,
                                  C.c_void_p(out.data_ptr() if n else None)), "nut_gather_u64")
         return out
+
+    def _gather_typed(self, col: torch.Tensor, idx, null) -> torch.Tensor:
+        if idx is not None and idx.dtype != torch.int64:
+            raise TypeError("gather takes an int64 index")
+        code = _NARROW[col.dtype]
+        odt = torch.float64 if code == L.T_F32 else torch.int64
+        n = col.numel() if idx is None else idx.numel()
+        out = torch.empty(n, dtype=odt, device=self.device)
+        nb = torch.tensor([null], dtype=odt).view(torch.int64).item() & 0xFFFFFFFFFFFFFFFF
+        self._bind_stream()
+        check(lib.nut_gather_typed(self.ctx, C.c_void_p(_col(col, self.device) if col.numel() else None), code,
+                                   C.c_void_p(idx.data_ptr() if idx is not None and n else None), n, nb,
+                                   C.c_void_p(out.data_ptr() if n else None)), "nut_gather_typed")
+        return out
+
+    def eval_rows(self, cols: list, progs: list, rows: torch.Tensor | None = None):
+        """Computed projections (nut_eval_rows): progs = [(value program, mask program or
+        None)] over `cols`, evaluated at the row ids `rows` (None: every row).  Returns
+        ([8-byte words as int64 tensors], [uint8 validity tensors])."""
+        q = ProgQuery(keys=[], cols=list(cols), aggs=[("sum", v, m) for v, m in progs])
+        spec = q.to_spec(self.device)
+        if rows is not None and rows.dtype != torch.int64:
+            raise TypeError("eval_rows takes int64 row ids")
+        m = int(spec.n) if rows is None else rows.numel()
+        outs = [torch.empty(max(m, 1), dtype=torch.int64, device=self.device) for _ in progs]
+        valid = [torch.empty(max(m, 1), dtype=torch.uint8, device=self.device) for _ in progs]
+        po = (C.c_void_p * len(progs))(*[o.data_ptr() for o in outs])
+        pv = (C.c_void_p * len(progs))(*[v.data_ptr() for v in valid])
+        self._bind_stream()
+        check(lib.nut_eval_rows(self.ctx, C.byref(spec), C.c_void_p(rows.data_ptr() if rows is not None and m else None),
+                                m, po, pv), "nut_eval_rows")
+        return [o[:m] for o in outs], [v[:m] for v in valid]
 
     def partition_i64(self, col: torch.Tensor, splitters, out: torch.Tensor | None = None):
         """Stable partition by bucket(k) = #{splitters <= k} (nut_partition_i64).  Returns

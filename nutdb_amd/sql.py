@@ -24,7 +24,12 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
+from . import _lib as _L
 from ._lib import (NUT_COL_HOST, NUT_OK, STMT_KINDS, TOKEN_TYPES, NutColumn, NutError, T_F64, T_I64, T_STR, check, lib)
+
+# column type names of Plan.route / Plan.prepare -> nut_type
+TYPE_NAMES = {"int64": T_I64, "float64": T_F64, "int32": _L.T_I32, "int16": _L.T_I16, "int8": _L.T_I8,
+              "uint32": _L.T_U32, "uint16": _L.T_U16, "uint8": _L.T_U8, "float32": _L.T_F32}
 
 NUT_ERR_PARSE = 6
 NUT_ERR_CAPACITY = 5
@@ -188,13 +193,14 @@ class Plan:
 
     def prepare(self, types: Dict[str, str]) -> None:
         """Compile an expression-mode plan's kernel ahead of execute (hipRTC, no GPU
-        needed); `types` = {column: "int64" | "float64"}.  No-op for fused plans."""
+        needed); `types` = {column: "int64" | "float64" | "int32" | "int16" | "int8" | "uint32" |
+        "uint16" | "uint8" | "float32"}.  No-op for fused plans."""
         arr = (NutColumn * max(len(types), 1))()
         names = [k.encode() for k in types]
         for i, (name, t) in enumerate(types.items()):
             arr[i].name = names[i]
             arr[i].data = None
-            arr[i].type = {"int64": T_I64, "float64": T_F64}[t]
+            arr[i].type = TYPE_NAMES[t]
         check(lib.nut_plan_prepare(self._h, arr, len(types)), "nut_plan_prepare")
 
     def route(self, types: Dict[str, str]) -> str:
@@ -206,7 +212,7 @@ class Plan:
         for i, (name, t) in enumerate(types.items()):
             arr[i].name = names[i]
             arr[i].data = None
-            arr[i].type = {"int64": T_I64, "float64": T_F64}[t]
+            arr[i].type = TYPE_NAMES[t]
         fn = lambda h, buf, cap, ln: lib.nut_plan_route(h, arr, len(types), buf, cap, ln)  # noqa: E731
         fn.__name__ = "nut_plan_route"
         return _text(fn, self._h)
@@ -269,8 +275,10 @@ class Plan:
                 typ = T_I64
             elif t.dtype == torch.float64:
                 typ = T_F64
-            else:
-                raise ValueError(f"column {name!r}: dtype {t.dtype} is not int64/float64")
+            else:  # narrow columns are read at their stored width
+                typ = TYPE_NAMES.get(str(t.dtype).replace("torch.", ""))
+                if typ is None:
+                    raise ValueError(f"column {name!r}: dtype {t.dtype} is not int64/float64 or a narrow numeric type")
             nb = name.encode()
             keep.append(nb)
             arr[i] = NutColumn(nb, t.data_ptr(), typ | (NUT_COL_HOST if host else 0))

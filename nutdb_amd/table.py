@@ -5,7 +5,8 @@
     t.sql("SELECT l_returnflag, sum(l_quantity) FROM lineitem GROUP BY l_returnflag")
 
 Columns live in HBM in the executed representation (int64 / f64); narrow integers and
-Float32 cross PCIe at their declared width and are widened on the GPU; strings are
+Float32 cross PCIe at their declared width and are widened on the GPU (or, in a
+Table(..., narrow=True), stay at that width in HBM and are widened in the kernels); strings are
 dictionary-encoded (codes feed the same int64 kernels; string constants in a query bind
 to codes; string group keys come back as str).
 """
@@ -28,12 +29,17 @@ _NP = {("int", 1): np.int8, ("int", 2): np.int16, ("int", 4): np.int32, ("int", 
 
 
 class Table:
-    def __init__(self, ex, create_sql: str):
+    def __init__(self, ex, create_sql: str, narrow: bool = False):
+        """narrow=True (nut_table_set_narrow): Int8/16/32, UInt8/16/32, Float32 and Boolean
+        columns keep their declared width in HBM (no widening pass on append); queries give
+        the same results either way."""
         self.ex = ex
         b = create_sql.encode("utf-8")
         h = C.c_void_p()
         check(lib.nut_table_create(b, len(b), C.byref(h)), "nut_table_create")
         self._h = h
+        if narrow:
+            self.set_narrow(True)
         nc = C.c_int()
         check(lib.nut_table_shape(h, C.byref(nc), None), "nut_table_shape")
         self.columns = {}
@@ -42,6 +48,19 @@ class Table:
             check(lib.nut_table_column_info(h, j, C.byref(nm), C.byref(kind), C.byref(width), C.byref(et)),
                   "nut_table_column_info")
             self.columns[nm.value.decode()] = (j, L.COL_KINDS[kind.value], width.value)
+
+    def set_narrow(self, on: bool = True) -> None:
+        """nut_table_set_narrow: only while the table has no rows (NutError otherwise)."""
+        check(lib.nut_table_set_narrow(self._h, int(on)), "nut_table_set_narrow")
+
+    def exec_types(self) -> Dict[str, int]:
+        """{column: nut_type its HBM column has} (narrow codes in a narrow table)"""
+        out = {}
+        for name, (j, _, _) in self.columns.items():
+            et = C.c_int()
+            check(lib.nut_table_column_info(self._h, j, None, None, None, C.byref(et)), "nut_table_column_info")
+            out[name] = et.value
+        return out
 
     @property
     def nrows(self) -> int:
