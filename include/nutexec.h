@@ -561,11 +561,14 @@ void nut_dist_destroy(nut_dist *d);
  * rank 0, NULL on every other member.  Every rank's spec has the same shape. */
 nut_status nut_dist_groupby(nut_dist *d, const nut_agg_spec *specs, uint64_t group_hint, nut_groups **out);
 /* ORDER BY k across ranks (config 5), sample sort: 4096 strided samples per rank ->
- * all-gather -> P-1 splitters at the pooled sample's quantiles -> nut_partition_i64 ->
+ * all-gather -> P-1 splitters at the pooled sample's quantiles -> range partition ->
  * ncclAllToAllv of keys -> local nut_sort_i64.  Member l ends with out_n[l] keys at
  * out[l] (device memory owned by the member, valid until its next nut_dist_* call):
  * the r-th key range of the global order, so the ranks' outputs concatenated in rank
- * order are sorted.  Keys equal to a splitter go to the higher rank.  P <= 64. */
+ * order are sorted.  Keys equal to a splitter value may be spread over several
+ * neighbouring ranks (skew-safe ranges: a key filling the sample quantiles of ranks
+ * a .. b is split over them; the ranks in between hold only that key), so equal keys
+ * need not share a rank; every key of rank r is still <= every key of rank r+1.  P <= 64. */
 nut_status nut_dist_sort_i64(nut_dist *d, const int64_t *const *in, const uint64_t *n, const int64_t **out,
                              uint64_t *out_n);
 /* SELECT col FROM t WHERE col <cmp> k over row shards (config 2): no data exchange;

@@ -133,8 +133,14 @@ struct nut_dist {
 namespace {
 
 constexpr int kMaxRanks = 64;  // nut_groups_partition / nut_partition_i64 bound
-constexpr size_t kHdrWords = 2 + 2 * kMaxRanks;
+// the widest header of any call at kMaxRanks ranks: the join's [status, build counts, probe
+// counts, 4 capacities].  Every call that builds a header asserts its width against this.
+constexpr size_t kHdrWords = 5 + 2 * kMaxRanks;
 constexpr size_t kHdrBytes = kHdrWords * kMaxRanks * 8;
+constexpr size_t hdr_groupby(size_t P) { return 4 + P; }
+constexpr size_t hdr_sort(size_t P) { return 3 + P; }
+constexpr size_t hdr_filter(size_t) { return 2; }
+constexpr size_t hdr_join(size_t P) { return 5 + 2 * P; }
 constexpr int kSamples = 4096;  // sample sort: strided samples per rank
 constexpr uint64_t kSampleWords = 2 + kSamples;  // one rank's all-gathered [status, has keys, samples]
 constexpr uint64_t kSortFlip = 1ull << 63;  // int64 order -> unsigned order
@@ -412,7 +418,8 @@ nut_status groupby_member(nut_dist *d, int l, const nut_agg_spec *spec, uint64_t
   }
   if (!st) st = nut_groups_partition(g, P, buf(mb, 0), n, counts.data());
   // header: [status, W, counts to each rank, capacity of buffers 1 and 2]
-  const size_t w = 4 + (size_t)P, cw = 2 + (size_t)P;
+  static_assert(hdr_groupby(kMaxRanks) <= kHdrWords, "the group-by header fits exchange_header at kMaxRanks");
+  const size_t w = hdr_groupby(P), cw = 2 + (size_t)P;
   std::vector<uint64_t> hdr(w, 0), all;
   hdr[1] = (uint64_t)W;
   for (int q = 0; q < P; ++q) hdr[2 + q] = counts[q];
@@ -721,7 +728,8 @@ nut_status sort_member(nut_dist *d, int l, const int64_t *in, uint64_t n, const 
   }
   for (int j = 0; j < nb; ++j) split_bucket(rg, (size_t)j, bcount[j], counts);
   // header: [status, counts to each rank, capacity of buffers 1 and 2]
-  const size_t w = 3 + (size_t)P;
+  static_assert(hdr_sort(kMaxRanks) <= kHdrWords, "the sort header fits exchange_header at kMaxRanks");
+  const size_t w = hdr_sort(P);
   hdr.assign(w, 0);
   for (int q = 0; q < P; ++q) hdr[1 + q] = counts[q];
   hdr[1 + P] = P == 1 ? ~0ull : cap_words(mb, 1);  // (one rank sorts its input in place of a copy)
@@ -786,7 +794,8 @@ nut_status filter_member(nut_dist *d, int l, const int64_t *col, uint64_t n, int
     *out_offset = 0;
     return st;
   }
-  std::vector<uint64_t> hdr(2, 0), all;
+  static_assert(hdr_filter(kMaxRanks) <= kHdrWords, "the filter header fits exchange_header at kMaxRanks");
+  std::vector<uint64_t> hdr(hdr_filter(d->nranks), 0), all;
   hdr[1] = cnt;
   st = exchange_header(d, l, st, hdr, all);
   if (st) return st;
@@ -835,7 +844,8 @@ nut_status join_member(nut_dist *d, int l, const int64_t *build, uint64_t nb, in
   if (!st) st = nut_hash_partition_i64(c, build, nb, P, brow0, (int64_t *)buf(mb, 0), (int64_t *)buf(mb, 1), bc.data());
   if (!st) st = nut_hash_partition_i64(c, probe, np, P, prow0, (int64_t *)buf(mb, 2), (int64_t *)buf(mb, 3), pc.data());
   // header: [status, build counts, probe counts, capacities of buffers 4..7]
-  const size_t w = 5 + 2 * (size_t)P;
+  static_assert(hdr_join(kMaxRanks) <= kHdrWords, "the join header fits exchange_header at kMaxRanks");
+  const size_t w = hdr_join(P);
   std::vector<uint64_t> hdr(w, 0), all;
   for (int q = 0; q < P; ++q) hdr[1 + q] = bc[q], hdr[1 + P + q] = pc[q];
   for (int k = 0; k < 4; ++k) hdr[1 + 2 * P + k] = cap_words(mb, 4 + k);
