@@ -102,6 +102,14 @@ __device__ __forceinline__ int64_t g_find(const GTable &t, uint64_t h, int64_t k
   const uint32_t tag = (uint32_t)(h >> 32);
   uint64_t word = kEmpty2;  // two-key: our published slot word once an arena entry is written
   for (uint64_t probe = 0; probe < t.cap; ++probe) {
+    // A launch that flagged overflow is discarded by the host (every caller runs again with a
+    // larger table, or fails): stop walking.  Claims go on past the limit, so with many more
+    // keys than slots the table fills up, and every further key then walked all `cap` slots,
+    // one atomic each (3e6 distinct keys regrown from a hint of 10: 120 s instead of
+    // milliseconds).  The check is reached only behind 63 occupied slots in a row, which a
+    // table below its limit hardly ever has; the flag is read at the memory side (rmw_load),
+    // so another XCD's update is seen.
+    if ((probe & 63) == 63 && (rmw_load(&t.ctl[1]) & 1u)) return -1;
     if (NK == 1) {
       uint64_t old = atomicCAS((unsigned long long *)&t.slot[s], (unsigned long long)kEmpty,
                                (unsigned long long)h);

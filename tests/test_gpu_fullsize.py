@@ -8,7 +8,8 @@ shapes themselves, not scaled-down stand-ins, checked against the C oracle.
   hash of the same generated column (a full element compare would need a 10 GB CPU sort).
 - config 3: GROUP BY key SUM(val) over 1e9 rows, G = 1000, dyadic values -> the f64 sums
   are exact, so the comparison is bit-exact.
-- config 4: the TPC-H Q1 shape over 1e9 rows (keys / counts exact, f64 sums <= 1e-12).
+- config 4: the TPC-H Q1 shape over 1e9 rows (keys / counts exact, f64 sums <= 1e-12), at
+  the launch shape the probe keeps and at the two 128-thread shapes it chooses among.
 - config 3 at large G (1e5 and 1e7 groups over 1e9 rows): the partitioned path the bench
   times (direct key-hash partitioning, one level at 1e5 and two at 1e7, optimistic level
   0), checked bit-exact against the indexed dense-array oracle (oracle.h
@@ -66,13 +67,23 @@ def test_groupby_full_config3(ex, orc):
     assert int(gw[:, 1].sum()) == n
 
 
-def test_q1_full_config4(ex, orc):
+def test_q1_full_config4(ex, orc, opts):
     from nutdb_amd.workloads import Q1_COLS, Q1_DATE_K, gen
     n = 1_000_000_000
     cols = [gen(ex, spec, n) for spec in Q1_COLS]
     g = ex.q1(*cols, date_k=Q1_DATE_K)
     gk, gw = g.to_host_words()
     g.free()
+    # the launch above ran the launch-shape probe (NUT_OPT_PRIV_PROBE) and the shape it kept
+    # for this device; the two 128-thread candidates it chooses among, on the same columns
+    forced = {}
+    for blocks in (3, 4):
+        opts(priv_bd=128, priv_blocks=blocks)
+        shape = ex.priv_shape()
+        assert (shape["threads"], shape["blocks_per_cu"]) == (128, blocks), shape
+        g = ex.q1(*cols, date_k=Q1_DATE_K)
+        forced[blocks] = g.to_host_words()
+        g.free()
     del cols
     sd, rf, ls, qty, price, disc = [orc.gen(spec, n) for spec in Q1_COLS]
     ok, ow = orc.groupby([rf, ls], [(0, 0, (0,)), (0, 0, (1,)), (0, 4, (1, 2)), (1, 0, ())],
@@ -83,6 +94,11 @@ def test_q1_full_config4(ex, orc):
     assert np.array_equal(gw[:, 3], ow[:, 3])
     for j in range(3):
         assert rel_err(gw[:, j].view(np.float64), ow[:, j].view(np.float64)) <= F64_SUM_RTOL
+    for blocks, (fk, fw) in forced.items():
+        assert np.array_equal(fk, ok), blocks
+        assert np.array_equal(fw[:, 3], ow[:, 3]), blocks
+        for j in range(3):
+            assert rel_err(fw[:, j].view(np.float64), ow[:, j].view(np.float64)) <= F64_SUM_RTOL, (blocks, j)
 
 
 @pytest.mark.parametrize("G,levels", [(100_000, 1), (10_000_000, 2)])
