@@ -282,7 +282,23 @@ typedef enum {
  *            by arg (nut_date_part): year, month 1-12, day of month, quarter 1-4, day of
  *            week (Monday = 1 .. Sunday = 7), day of year 1-366, year * 100 + month,
  *            year * 10000 + month * 100 + day (toYYYYMM / toYYYYMMDD); d is first clamped to
- *            [-2^40, 2^40] (beyond any real date), so every d has one defined result. */
+ *            [-2^40, 2^40] (beyond any real date), so every d has one defined result.
+ *            REL_MONTH = year * 12 + month, REL_QUARTER = year * 4 + (month - 1) / 3 and
+ *            REL_WEEK = floor((d + 3) / 7) (weeks start on Monday) count periods from a
+ *            fixed origin: their differences are dateDiff in months, quarters and weeks.
+ * The calendar ops below take int operands only and give ints.  Operands are clamped first
+ * (days to +-2^40, seconds to +-2^40 * 86400, month counts to +-2^36), so every int64 has
+ * one defined result; fdiv / fmod are floor division and modulo by a positive constant.
+ *   TIMEPART one operand s = seconds since 1970-01-01 00:00:00, by arg (nut_time_part):
+ *            DATE = fdiv(s, 86400) (the day number), HOUR = fmod(s, 86400) / 3600, MINUTE =
+ *            fmod(s, 3600) / 60, SECOND = fmod(s, 60); START_MINUTE, START_FIVE_MINUTES,
+ *            START_FIFTEEN_MINUTES, START_HOUR, START_DAY = s - fmod(s, g), g = 60, 300,
+ *            900, 3600, 86400 (seconds)
+ *   DATETRUNC one operand d = days, by arg (nut_date_trunc), a day number: WEEK_MONDAY =
+ *            d - fmod(d + 3, 7), WEEK_SUNDAY = d - fmod(d + 4, 7); MONTH, QUARTER, YEAR = the
+ *            first day of d's month, quarter, year; MONTH_END = the last day of d's month
+ *   ADDMONTHS pops d (days), n (months): the day number of the proleptic Gregorian date n
+ *            months from d, the day of month clamped to the target month's length */
 typedef enum {
   NUT_P_COL = 0, NUT_P_I64 = 1, NUT_P_F64 = 2,
   NUT_P_ADD = 3, NUT_P_SUB = 4, NUT_P_MUL = 5, NUT_P_DIV = 6, NUT_P_MOD = 7, NUT_P_INTDIV = 8,
@@ -291,16 +307,25 @@ typedef enum {
   NUT_P_BITAND = 19, NUT_P_BITOR = 20, NUT_P_BITXOR = 21, NUT_P_BITNOT = 22,
   NUT_P_SHL = 23, NUT_P_SHR = 24,
   NUT_P_IF = 25, NUT_P_ABS = 26, NUT_P_TO_F64 = 27, NUT_P_LOOKUP = 28, NUT_P_DATEPART = 29,
-  NUT_P_MAP = 30
+  NUT_P_MAP = 30, NUT_P_TIMEPART = 31, NUT_P_DATETRUNC = 32, NUT_P_ADDMONTHS = 33
 } nut_prog_op;
 typedef enum {
   NUT_DP_YEAR = 0, NUT_DP_MONTH = 1, NUT_DP_DAY = 2, NUT_DP_QUARTER = 3, NUT_DP_WEEKDAY = 4, NUT_DP_YEARDAY = 5,
-  NUT_DP_YYYYMM = 6, NUT_DP_YYYYMMDD = 7
+  NUT_DP_YYYYMM = 6, NUT_DP_YYYYMMDD = 7, NUT_DP_REL_MONTH = 8, NUT_DP_REL_QUARTER = 9, NUT_DP_REL_WEEK = 10
 } nut_date_part;
+typedef enum {
+  NUT_TP_DATE = 0, NUT_TP_HOUR = 1, NUT_TP_MINUTE = 2, NUT_TP_SECOND = 3, NUT_TP_START_MINUTE = 4,
+  NUT_TP_START_FIVE_MINUTES = 5, NUT_TP_START_FIFTEEN_MINUTES = 6, NUT_TP_START_HOUR = 7, NUT_TP_START_DAY = 8
+} nut_time_part;
+typedef enum {
+  NUT_DT_WEEK_MONDAY = 0, NUT_DT_WEEK_SUNDAY = 1, NUT_DT_MONTH = 2, NUT_DT_QUARTER = 3, NUT_DT_YEAR = 4,
+  NUT_DT_MONTH_END = 5
+} nut_date_trunc;
 typedef enum { NUT_PT_I64 = 0, NUT_PT_F64 = 1, NUT_PT_BOOL = 2 } nut_prog_value_type;
 typedef struct {
   int32_t op;   /* nut_prog_op */
-  int32_t arg;  /* NUT_P_COL: column index; NUT_P_LOOKUP / MAP: table length; NUT_P_DATEPART: part */
+  int32_t arg;  /* NUT_P_COL: column index; NUT_P_LOOKUP / MAP: table length;
+                   NUT_P_DATEPART / TIMEPART / DATETRUNC: the part (nut_date_part / nut_time_part / nut_date_trunc) */
   int64_t v;    /* NUT_P_I64 / NUT_P_F64 constant; NUT_P_LOOKUP / MAP: table address */
 } nut_prog_node;
 typedef struct {
@@ -647,13 +672,21 @@ typedef enum { NUT_PLAN_FILTER = 0, NUT_PLAN_GROUPBY = 1, NUT_PLAN_SORT = 2 } nu
 typedef struct {
   const char *name;   /* column name as written in the SQL (ASCII case-insensitive match) */
   const void *data;   /* device pointer, nrows elements (host pointer with NUT_COL_HOST) */
-  int32_t type;       /* nut_type, optionally | NUT_COL_HOST */
+  int32_t type;       /* nut_type, optionally | NUT_COL_HOST | NUT_COL_AS_DATE or NUT_COL_AS_DATETIME */
 } nut_column;
 /* OR-ed into nut_column.type: `data` is host memory (pageable or page-locked).  The
  * nut_plan_execute* calls copy such a column into HBM on the context's stream (8 B x nrows
  * over PCIe) before running the plan and free the copy before they return; the caller
  * keeps ownership.  Device-resident columns are read in place. */
 #define NUT_COL_HOST 0x100
+/* OR-ed into nut_column.type of an int64 column: its temporal kind.  AS_DATE: day numbers;
+ * AS_DATETIME: seconds since 1970-01-01 00:00:00.  SQL day functions (toYear .. toYYYYMMDD,
+ * toStartOfMonth, addMonths, ...) take the day of a Datetime first; time functions (toHour,
+ * toStartOfHour, ...) reject a Date.  Without a flag a column is a plain integer: day
+ * functions read it as days and time functions as seconds.  Typed tables (nut_table) pass
+ * their Date / Datetime columns' kinds themselves. */
+#define NUT_COL_AS_DATE 0x200
+#define NUT_COL_AS_DATETIME 0x400
 
 nut_status nut_sql_plan(const char *sql, size_t len, nut_plan **out);
 int nut_plan_kind_of(const nut_plan *plan);

@@ -30,6 +30,8 @@ NUT_OK = 0
 NUT_ERR_CAPACITY = 5
 NUT_JOIN_ANY_ORDER = 0x100
 NUT_COL_HOST = 0x100
+NUT_COL_AS_DATE = 0x200      # an int64 column of day numbers
+NUT_COL_AS_DATETIME = 0x400  # an int64 column of seconds since 1970-01-01
 STATUS_NAMES = {
     0: "NUT_OK", 1: "NUT_ERR_INVALID_ARG", 2: "NUT_ERR_HIP", 3: "NUT_ERR_OOM",
     4: "NUT_ERR_UNSUPPORTED", 5: "NUT_ERR_CAPACITY", 6: "NUT_ERR_PARSE", 7: "NUT_ERR_PLAN",
@@ -50,9 +52,15 @@ EX_COL, EX_MUL, EX_ADD, EX_SUB, EX_MUL_1M, EX_MUL_1M_1P = range(6)
 # nut_prog_op (expression programs, RPN) and nut_prog_value_type
 PROG_OPS = ["col", "i64", "f64", "add", "sub", "mul", "div", "mod", "intdiv", "lt", "le", "gt", "ge", "eq", "ne",
             "and", "or", "xor", "not", "bitand", "bitor", "bitxor", "bitnot", "shl", "shr", "if", "abs", "to_f64", "lookup",
-            "datepart"]
+            "datepart", "map", "timepart", "datetrunc", "addmonths"]
 # nut_date_part (the arg of a "datepart" node)
 DP_YEAR, DP_MONTH, DP_DAY, DP_QUARTER, DP_WEEKDAY, DP_YEARDAY, DP_YYYYMM, DP_YYYYMMDD = range(8)
+DP_REL_MONTH, DP_REL_QUARTER, DP_REL_WEEK = 8, 9, 10
+# nut_time_part (the arg of a "timepart" node: its operand is seconds)
+(TP_DATE, TP_HOUR, TP_MINUTE, TP_SECOND, TP_START_MINUTE, TP_START_FIVE_MINUTES, TP_START_FIFTEEN_MINUTES,
+ TP_START_HOUR, TP_START_DAY) = range(9)
+# nut_date_trunc (the arg of a "datetrunc" node: its operand is days)
+DT_WEEK_MONDAY, DT_WEEK_SUNDAY, DT_MONTH, DT_QUARTER, DT_YEAR, DT_MONTH_END = range(6)
 P = {name: i for i, name in enumerate(PROG_OPS)}
 PT_I64, PT_F64, PT_BOOL = 0, 1, 2
 

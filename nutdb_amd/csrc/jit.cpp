@@ -75,9 +75,10 @@ struct Gen {
       PVal a[3];
       const int op = nd.op;
       const int arity = op <= NUT_P_F64 ? 0 : (op == NUT_P_NOT || op == NUT_P_BITNOT || op == NUT_P_ABS ||
-                                                op == NUT_P_TO_F64 || op == NUT_P_LOOKUP || op == NUT_P_DATEPART || op == NUT_P_MAP) ? 1
+                                                op == NUT_P_TO_F64 || op == NUT_P_LOOKUP || op == NUT_P_DATEPART || op == NUT_P_MAP ||
+                                                op == NUT_P_TIMEPART || op == NUT_P_DATETRUNC) ? 1
                                                                                          : op == NUT_P_IF ? 3 : 2;
-      if (op < 0 || op > NUT_P_MAP) return fail("unknown program op " + std::to_string(op));
+      if (op < 0 || op > NUT_P_ADDMONTHS) return fail("unknown program op " + std::to_string(op));
       if (!pop(arity, a)) return fail("program stack underflow at node " + std::to_string(i));
       PVal r;
       const bool f = arity == 2 && (a[0].t == NUT_PT_F64 || a[1].t == NUT_PT_F64);
@@ -179,8 +180,22 @@ struct Gen {
           break;
         case NUT_P_DATEPART:
           if (a[0].t == NUT_PT_F64) return fail("DATEPART needs an integer operand (days)");
-          if (nd.arg < NUT_DP_YEAR || nd.arg > NUT_DP_YYYYMMDD) return fail("DATEPART: unknown part " + std::to_string(nd.arg));
+          if (nd.arg < NUT_DP_YEAR || nd.arg > NUT_DP_REL_WEEK) return fail("DATEPART: unknown part " + std::to_string(nd.arg));
           r = {NUT_PT_I64, "jdatepart(" + as_i(a[0]) + ", " + std::to_string(nd.arg) + ")"};
+          break;
+        case NUT_P_TIMEPART:
+          if (a[0].t == NUT_PT_F64) return fail("TIMEPART needs an integer operand (seconds)");
+          if (nd.arg < NUT_TP_DATE || nd.arg > NUT_TP_START_DAY) return fail("TIMEPART: unknown part " + std::to_string(nd.arg));
+          r = {NUT_PT_I64, "jtimepart(" + as_i(a[0]) + ", " + std::to_string(nd.arg) + ")"};
+          break;
+        case NUT_P_DATETRUNC:
+          if (a[0].t == NUT_PT_F64) return fail("DATETRUNC needs an integer operand (days)");
+          if (nd.arg < NUT_DT_WEEK_MONDAY || nd.arg > NUT_DT_MONTH_END) return fail("DATETRUNC: unknown unit " + std::to_string(nd.arg));
+          r = {NUT_PT_I64, "jdatetrunc(" + as_i(a[0]) + ", " + std::to_string(nd.arg) + ")"};
+          break;
+        case NUT_P_ADDMONTHS:
+          if (f) return fail("ADDMONTHS needs integer operands (days, months)");
+          r = {NUT_PT_I64, "jaddmonths(" + as_i(a[0]) + ", " + as_i(a[1]) + ")"};
           break;
       }
       if (r.s.size() > (1u << 20)) return fail("expression program too large");
@@ -239,31 +254,106 @@ __device__ __forceinline__ int64_t jmap(int64_t x, uint64_t t, uint64_t n) {
   if ((uint64_t)x >= n) return -1;
   return ((const int64_t *)t)[x];
 }
-// civil-from-days (proleptic Gregorian); P = nut_date_part.  d is clamped to +-2^40 days
-// first, so no intermediate overflows.
-__device__ __forceinline__ int64_t jdatepart(int64_t d, const int P) {
-  d = d < -(1ll << 40) ? -(1ll << 40) : d > (1ll << 40) ? (1ll << 40) : d;
+// ---- calendar (proleptic Gregorian; day 0 = 1970-01-01).  Every divisor is a literal: the
+// compiler turns each division into multiplies and shifts (the device has no 64-bit divide).
+__device__ __forceinline__ int64_t jclamp(int64_t x, const int64_t m) { return x < -m ? -m : x > m ? m : x; }
+// floor division by a positive literal g, and the remainder in [0, g)
+__device__ __forceinline__ int64_t jfdiv(int64_t a, const int64_t g) {
+  const int64_t q = a / g;
+  return a - q * g < 0 ? q - 1 : q;
+}
+__device__ __forceinline__ int64_t jfrem(int64_t a, const int64_t g) { return a - jfdiv(a, g) * g; }
+// a civil date: year = y400 + yr (y400 a multiple of 400, yr in [0, 400]), month 1-12, day
+// of month 1-31; doy / mp = day and month of the year that starts on March 1
+struct JDate {
+  int64_t y400;
+  uint32_t yr, m, d, doy, mp;
+};
+__device__ __forceinline__ bool jleap(uint32_t yr) { return (yr % 4 == 0 && yr % 100 != 0) || yr % 400 == 0; }
+__device__ __forceinline__ uint32_t jmonth_days(uint32_t yr, uint32_t m) {
+  return m == 2 ? (jleap(yr) ? 29u : 28u) : 30u + ((m + (m >> 3)) & 1u);
+}
+// civil-from-days of a clamped day number: one 64-bit division, the rest in 32 bits
+__device__ __forceinline__ JDate jcivil(int64_t d) {
   const int64_t z = d + 719468;
-  const int64_t era = (z >= 0 ? z : z - 146096) / 146097;
-  const int64_t doe = z - era * 146097;
-  const int64_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
-  const int64_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);  // from March 1
-  const int64_t mp = (5 * doy + 2) / 153;
-  const int64_t m = mp < 10 ? mp + 3 : mp - 9;
-  const int64_t y = yoe + era * 400 + (m <= 2 ? 1 : 0);
+  const int64_t era = jfdiv(z, 146097);
+  const uint32_t doe = (uint32_t)(z - era * 146097);
+  const uint32_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
+  JDate c;
+  c.doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
+  c.mp = (5 * c.doy + 2) / 153;
+  c.d = c.doy - (153 * c.mp + 2) / 5 + 1;
+  c.m = c.mp < 10 ? c.mp + 3 : c.mp - 9;
+  c.y400 = era * 400;
+  c.yr = yoe + (c.m <= 2 ? 1u : 0u);
+  return c;
+}
+// days-from-civil of year y400 + yr (yr in [0, 400)), month m, day d
+__device__ __forceinline__ int64_t jdays(int64_t y400, uint32_t yr, uint32_t m, uint32_t d) {
+  if (m <= 2) {  // January and February belong to the March-based year before
+    if (yr == 0) y400 -= 400, yr = 399;
+    else yr -= 1;
+  }
+  const uint32_t doy = (153 * (m > 2 ? m - 3 : m + 9) + 2) / 5 + d - 1;
+  const uint32_t doe = yr * 365 + yr / 4 - yr / 100 + doy;
+  return (y400 / 400) * 146097 + (int64_t)doe - 719468;
+}
+// P = nut_date_part.  d is clamped to +-2^40 days first, so no intermediate overflows.
+__device__ __forceinline__ int64_t jdatepart(int64_t d, const int P) {
+  d = jclamp(d, 1ll << 40);
+  if (P == 4) return jfrem(d + 3, 7) + 1;  // 1970-01-01 was a Thursday (4)
+  if (P == 10) return jfdiv(d + 3, 7);
+  const JDate c = jcivil(d);
+  const int64_t y = c.y400 + (int64_t)c.yr, m = c.m;
   if (P == 0) return y;
   if (P == 1) return m;
-  if (P == 2) return doy - (153 * mp + 2) / 5 + 1;
+  if (P == 2) return c.d;
   if (P == 6) return y * 100 + m;
-  if (P == 7) return y * 10000 + m * 100 + (doy - (153 * mp + 2) / 5 + 1);
+  if (P == 7) return y * 10000 + m * 100 + c.d;
   if (P == 3) return (m - 1) / 3 + 1;
-  if (P == 4) {  // 1970-01-01 was a Thursday (4)
-    int64_t w = d % 7;
-    w = w < 0 ? w + 7 : w;
-    return (w + 3) % 7 + 1;
-  }
+  if (P == 8) return y * 12 + m;
+  if (P == 9) return y * 4 + (m - 1) / 3;
   // day of year: January / February are days 306.. of the March-based year
-  return doy >= 306 ? doy - 305 : doy + 60 + (((y % 4 == 0 && y % 100 != 0) || y % 400 == 0) ? 1 : 0);
+  return c.doy >= 306 ? (int64_t)c.doy - 305 : (int64_t)c.doy + 60 + (jleap(c.yr) ? 1 : 0);
+}
+// P = nut_time_part; s (seconds) is clamped to +-2^40 days first
+__device__ __forceinline__ int64_t jtimepart(int64_t s, const int P) {
+  s = jclamp(s, (1ll << 40) * 86400);
+  if (P == 0) return jfdiv(s, 86400);
+  if (P == 1) return jfrem(s, 86400) / 3600;
+  if (P == 2) return jfrem(s, 3600) / 60;
+  if (P == 3) return jfrem(s, 60);
+  if (P == 4) return s - jfrem(s, 60);
+  if (P == 5) return s - jfrem(s, 300);
+  if (P == 6) return s - jfrem(s, 900);
+  if (P == 7) return s - jfrem(s, 3600);
+  return s - jfrem(s, 86400);
+}
+// P = nut_date_trunc; a day number
+__device__ __forceinline__ int64_t jdatetrunc(int64_t d, const int P) {
+  d = jclamp(d, 1ll << 40);
+  if (P == 0) return d - jfrem(d + 3, 7);
+  if (P == 1) return d - jfrem(d + 4, 7);
+  const JDate c = jcivil(d);
+  if (P == 2) return d - (int64_t)c.d + 1;
+  if (P == 5) return d - (int64_t)c.d + (int64_t)jmonth_days(c.yr, c.m);
+  const int64_t jan1 = c.doy >= 306 ? d - ((int64_t)c.doy - 306) : d - ((int64_t)c.doy + 59 + (jleap(c.yr) ? 1 : 0));
+  if (P == 4) return jan1;
+  // quarter: April, July and October start on days 31, 122 and 214 of the March-based year
+  if (c.m <= 3) return jan1;
+  const uint32_t q0 = c.m <= 6 ? 31u : c.m <= 9 ? 122u : 214u;
+  return d - (int64_t)c.doy + (int64_t)q0;
+}
+// n months from day d, the day of month clamped to the target month's length
+__device__ __forceinline__ int64_t jaddmonths(int64_t d, int64_t n) {
+  d = jclamp(d, 1ll << 40);
+  n = jclamp(n, 1ll << 36);
+  const JDate c = jcivil(d);
+  const int64_t t = (c.y400 + (int64_t)c.yr) * 12 + ((int64_t)c.m - 1) + n;
+  const int64_t e = jfdiv(t, 4800);  // 400 years of months
+  const uint32_t r = (uint32_t)(t - e * 4800), yr = r / 12, m = r - yr * 12 + 1;
+  const uint32_t md = jmonth_days(yr, m);
+  return jdays(e * 400, yr, m, c.d < md ? c.d : md);
 }
 )";
 

@@ -552,7 +552,7 @@ bool narrow_groupby_plan(const nut_plan &p, const nut_column *const *bound, nut_
   }
   // a narrow integer key is a computed key: its one-node program, evaluated in the kernel
   for (size_t j = 0; j < q.keys.size(); ++j)
-    if (q.keys[j] >= 0 && col_narrow(bound[q.keys[j]]) && !type_is_float(bound[q.keys[j]]->type)) q.keys[j] = -1;
+    if (q.keys[j] >= 0 && col_narrow(bound[q.keys[j]]) && !type_is_float(col_type(bound[q.keys[j]]))) q.keys[j] = -1;
   return true;
 }
 
@@ -571,7 +571,7 @@ nut_status exec_groupby(nut_ctx *c, const nut_plan &p0, const nut_column *const 
     if (k < 0 || !col_narrow(nb[k])) continue;  // (narrow and still a plain key: Float32)
     wide.emplace_back();
     if (wide.back().alloc(c, std::max<uint64_t>(n, 1) * 8) != hipSuccess) return fail(NUT_ERR_OOM, "hipMalloc (Float32 key)");
-    nut_status st = nut_gather_typed(c, nb[k]->data, nb[k]->type, nullptr, n, 0, (uint64_t *)wide.back().p);
+    nut_status st = nut_gather_typed(c, nb[k]->data, col_type(nb[k]), nullptr, n, 0, (uint64_t *)wide.back().p);
     if (st) return st;
     widec.push_back(nut_column{nb[k]->name, wide.back().p, NUT_T_F64});
     nb[k] = &widec.back();
@@ -580,7 +580,7 @@ nut_status exec_groupby(nut_ctx *c, const nut_plan &p0, const nut_column *const 
   std::vector<char> fkey(p.keys.size(), 0);
   bool any = false;
   for (size_t j = 0; j < p.keys.size(); ++j)
-    if (p.keys[j] >= 0 && bound[p.keys[j]]->type == NUT_T_F64 && !(dicts && dicts[p.keys[j]])) fkey[j] = 1, any = true;
+    if (p.keys[j] >= 0 && col_type(bound[p.keys[j]]) == NUT_T_F64 && !(dicts && dicts[p.keys[j]])) fkey[j] = 1, any = true;
   if (!any) return groupby_bound(c, p, bound, dicts, n, hint, r, fkey);
   nut_plan q = p;
   std::vector<const nut_column *> b(bound, bound + p.cols.size());

@@ -215,7 +215,7 @@ nut_status exec_join(nut_ctx *c, const nut_plan &p, const nut_column *lc, int nl
     side[i] = a ? 0 : 1;
     src[i] = a ? a : b;
     sdict[i] = a ? (ldict ? ldict[a - lc] : nullptr) : (rdict ? rdict[b - rc] : nullptr);
-    if (src[i]->type != NUT_T_I64 && src[i]->type != NUT_T_F64)
+    if (col_type(src[i]) != NUT_T_I64 && col_type(src[i]) != NUT_T_F64)
       return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute2: column '" + p.cols[i] + "' has an unknown type");
     if ((a ? lrows : rrows) && !src[i]->data)
       return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute2: column '" + p.cols[i] + "' is NULL");
@@ -223,7 +223,7 @@ nut_status exec_join(nut_ctx *c, const nut_plan &p, const nut_column *lc, int nl
   const int k0 = p.jkey[0], k1 = p.jkey[1];
   if (side[k0] == side[k1]) return fail(NUT_ERR_PLAN, "JOIN ON must compare a column of each table");
   const nut_column *lkey = side[k0] == 0 ? src[k0] : src[k1], *rkey = side[k0] == 0 ? src[k1] : src[k0];
-  if (lkey->type != NUT_T_I64 || rkey->type != NUT_T_I64) return fail(NUT_ERR_PLAN, "JOIN keys must be int64 columns");
+  if (col_type(lkey) != NUT_T_I64 || col_type(rkey) != NUT_T_I64) return fail(NUT_ERR_PLAN, "JOIN keys must be int64 columns");
   if (sdict[k0] || sdict[k1])  // codes of two dictionaries do not compare
     return fail(NUT_ERR_PLAN, "JOIN keys must be integer columns (string keys are not executed)");
   // INNER builds the smaller table (decided after the pushdown below); the outer / semi /
@@ -485,7 +485,7 @@ nut_status residual_semi(nut_ctx *c, const nut_plan &p, int k, int op, const nut
     gs.keys[0] = bk;
     gs.nvals = 1;
     gs.val_col[0] = ic;
-    gs.val_type[0] = icol->type;
+    gs.val_type[0] = col_type(icol);
     gs.naggs = 2;
     gs.agg_op[0] = NUT_AGG_MIN;
     gs.agg_op[1] = NUT_AGG_MAX;
@@ -635,7 +635,7 @@ nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *ta
     if (!col) return fail(NUT_ERR_INVALID_ARG, "nut_plan_executen: column '" + nm + "' is not bound");
     if (sc > 0 && tscope[hit] != 0 && tscope[hit] != sc)
       return fail(NUT_ERR_PLAN, "a subquery reads column '" + nm + "' of another subquery's table");
-    if (col->type != NUT_T_I64 && col->type != NUT_T_F64)
+    if (col_type(col) != NUT_T_I64 && col_type(col) != NUT_T_F64)
       return fail(NUT_ERR_INVALID_ARG, "nut_plan_executen: column '" + nm + "' has an unknown type");
     if (nrows[hit] && !col->data) return fail(NUT_ERR_INVALID_ARG, "nut_plan_executen: column '" + nm + "' is NULL");
     side[i] = hit;
@@ -694,7 +694,7 @@ nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *ta
         std::swap(a, b);
         op = op == NUT_P_LT ? NUT_P_GT : op == NUT_P_GT ? NUT_P_LT : op == NUT_P_LE ? NUT_P_GE : op == NUT_P_GE ? NUT_P_LE : op;
       }
-      if (op == NUT_P_EQ && jkey[k][0] < 0 && src[a]->type == NUT_T_I64 && src[b]->type == NUT_T_I64) {
+      if (op == NUT_P_EQ && jkey[k][0] < 0 && col_type(src[a]) == NUT_T_I64 && col_type(src[b]) == NUT_T_I64) {
         jkey[k] = {b, a};
       } else if (res[k].op < 0 && op != NUT_P_EQ) {
         res[k] = Residual{op, a, b};
@@ -714,7 +714,7 @@ nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *ta
     else if (side[b] == t && side[a] < t) knew[k] = b, kold[k] = a;
     else return fail(NUT_ERR_PLAN, "JOIN " + std::to_string(t) + ": ON must compare a column of '" + tname[t] +
                                        "' with a column of an earlier table");
-    if (src[a]->type != NUT_T_I64 || src[b]->type != NUT_T_I64) return fail(NUT_ERR_PLAN, "JOIN keys must be int64 columns");
+    if (col_type(src[a]) != NUT_T_I64 || col_type(src[b]) != NUT_T_I64) return fail(NUT_ERR_PLAN, "JOIN keys must be int64 columns");
     if (sdict[a] || sdict[b])  // codes of two dictionaries do not compare
       return fail(NUT_ERR_PLAN, "JOIN " + std::to_string(t) + ": string keys are not executed (each table has its own "
                                     "dictionary)");
@@ -1016,7 +1016,7 @@ nut_status widen_cols(nut_ctx *c, const nut_column *cols, int n, uint64_t rows, 
   copy.assign(cols, cols + n);
   for (nut_column &col : copy) {
     if (!col_narrow(&col)) continue;
-    const int t = col.type;
+    const int t = col_type(&col);  // (a narrow column has no temporal kind)
     col.type = logical_type(t);
     if (!rows || !col.data) continue;
     bufs.emplace_back();
@@ -1040,7 +1040,7 @@ nut_status stage_host(nut_ctx *c, const nut_column *cols, int n, uint64_t rows, 
     col.type &= ~NUT_COL_HOST;
     if (!rows || !col.data) continue;
     hs.bufs.emplace_back();
-    const size_t bytes = rows * (size_t)(type_known(col.type) ? type_width(col.type) : 8);  // the declared width
+    const size_t bytes = rows * (size_t)(type_known(col_type(&col)) ? type_width(col_type(&col)) : 8);  // the declared width
     NUT_HIP(hs.bufs.back().alloc(c, bytes));
     NUT_HIP(hipMemcpyAsync(hs.bufs.back().p, col.data, bytes, hipMemcpyHostToDevice, c->stream));
     col.data = hs.bufs.back().p;

@@ -131,7 +131,7 @@ nut_status exec_sort_rows(nut_ctx *c, const nut_plan &p, const nut_column *const
                : -1;
     if (dc >= 0 && dicts && dicts[dc]) sdict[j] = dc;
     r->names.push_back(p.outs[j].name);
-    r->types.push_back(sdict[j] >= 0 ? NUT_T_STR : p.projs[j] >= 0 ? logical_type(bound[p.projs[j]]->type) : ctype[j]);
+    r->types.push_back(sdict[j] >= 0 ? NUT_T_STR : p.projs[j] >= 0 ? logical_type(col_type(bound[p.projs[j]])) : ctype[j]);
   }
   uint64_t cnt = 0;
   DevBuf rows, perm, keys;
@@ -158,7 +158,7 @@ nut_status exec_sort_rows(nut_ctx *c, const nut_plan &p, const nut_column *const
     nut_status s = gather_col(c, kc, (const int64_t *)rows.p, cnt, (uint64_t *)keys.p);
     DevBuf pos;
     uint64_t m2 = cnt;
-    if (!s) s = topk_reduce(c, p, keys.p, logical_type(kc->type), p.sort_keys[0].second, cnt, pos, &m2);
+    if (!s) s = topk_reduce(c, p, keys.p, logical_type(col_type(kc)), p.sort_keys[0].second, cnt, pos, &m2);
     if (s) return s;
     if (m2 < cnt) {
       NUT_HIP(perm.alloc(c, std::max<uint64_t>(m2, 1) * 8));
@@ -185,7 +185,7 @@ nut_status exec_sort_rows(nut_ctx *c, const nut_plan &p, const nut_column *const
     for (size_t i = p.sort_keys.size(); i-- > 0 && !s;) {
       const nut_column *kc = bound[p.sort_keys[i].first];
       s = gather_col(c, kc, (const int64_t *)rows.p, cnt, (uint64_t *)keys.p);
-      if (!s) s = nut_sort_pairs(c, keys.p, logical_type(kc->type), p.sort_keys[i].second ? 1 : 0, (const int64_t *)rows.p,
+      if (!s) s = nut_sort_pairs(c, keys.p, logical_type(col_type(kc)), p.sort_keys[i].second ? 1 : 0, (const int64_t *)rows.p,
                                  (int64_t *)perm.p, cnt);
       std::swap(rows.p, perm.p);  // the sorted row ids feed the next (more significant) key
     }
@@ -246,7 +246,7 @@ nut_status scan_route(const nut_plan &p, const nut_column *const *bound, const D
       if (dicts && dicts[k.first])
         return fail(NUT_ERR_PLAN, "ORDER BY string column '" + p.cols[k.first] + "' is not executed (dictionary codes "
                                   "are in first-seen order)");
-      if (!type_known(bound[k.first]->type))
+      if (!type_known(col_type(bound[k.first])))
         return fail(NUT_ERR_PLAN, "ORDER BY column '" + p.cols[k.first] + "' must be int64 or float64");
     }
     *route = S_ROWID;
@@ -255,9 +255,9 @@ nut_status scan_route(const nut_plan &p, const nut_column *const *bound, const D
   // (a narrow column of any type reruns too: only the generated scan kernel and the typed
   // gather read narrow bytes, never the fused filter / sort)
   bool f64 = false, narrow = false;
-  for (int pj : p.projs) f64 = f64 || type_is_float(bound[pj]->type), narrow = narrow || col_narrow(bound[pj]);
+  for (int pj : p.projs) f64 = f64 || type_is_float(col_type(bound[pj])), narrow = narrow || col_narrow(bound[pj]);
   for (const PlanPred &pr : p.preds)
-    f64 = f64 || type_is_float(bound[pr.col]->type), narrow = narrow || col_narrow(bound[pr.col]);
+    f64 = f64 || type_is_float(col_type(bound[pr.col])), narrow = narrow || col_narrow(bound[pr.col]);
   if (!p.compiled && (f64 || narrow || (p.kind == NUT_PLAN_FILTER && dicts && dicts[p.proj]))) {
     *route = S_RERUN_EXPR;
     return NUT_OK;
@@ -269,7 +269,7 @@ nut_status scan_route(const nut_plan &p, const nut_column *const *bound, const D
   for (const PlanPred &pr : p.preds)
     if (pr.c.is_str) return fail(NUT_ERR_PLAN, "string constant " + cval_str(pr.c) + " compared with an int64 column");
   for (int pj : p.projs)
-    if (!type_known(bound[pj]->type) || (logical_type(bound[pj]->type) != NUT_T_I64 && !p.compiled))
+    if (!type_known(col_type(bound[pj])) || (logical_type(col_type(bound[pj])) != NUT_T_I64 && !p.compiled))
       return fail(NUT_ERR_PLAN, "column '" + p.cols[pj] + "' must be int64 or float64 for this scan/sort");
   if (p.compiled)
     *route = p.kind == NUT_PLAN_FILTER ? S_EXPR_FILTER : f64 ? S_EXPR_SORT_F64 : S_EXPR_SORT;
@@ -302,7 +302,7 @@ nut_status exec_scan(nut_ctx *c, const nut_plan &p, const nut_column *const *bou
   const nut_column *col = bound[p.proj];
   for (size_t j = 0; j < p.projs.size(); ++j) {
     r->names.push_back(p.outs[j].name);
-    r->types.push_back(dicts && dicts[p.projs[j]] ? NUT_T_STR : logical_type(bound[p.projs[j]]->type));
+    r->types.push_back(dicts && dicts[p.projs[j]] ? NUT_T_STR : logical_type(col_type(bound[p.projs[j]])));
   }
   int op = NUT_GE;
   int64_t k = INT64_MIN;  // no predicate: every row passes
@@ -540,7 +540,7 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
   s.nkeys = keyprog ? 0 : (int32_t)p.keys.size();
   for (size_t j = 0; j < p.keys.size() && !keyprog; ++j) {
     const nut_column *k = bound[p.keys[j]];
-    if (k->type != NUT_T_I64) return fail(NUT_ERR_PLAN, "GROUP BY column '" + p.cols[p.keys[j]] + "' must be int64");
+    if (col_type(k) != NUT_T_I64) return fail(NUT_ERR_PLAN, "GROUP BY column '" + p.cols[p.keys[j]] + "' must be int64");
     s.keys[j] = (const int64_t *)k->data;
   }
   agg_f64.assign(p.aggs.size(), 0);
@@ -553,7 +553,7 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
         if (s.nprog_cols >= NUT_MAX_PROG_COLS) return fail(NUT_ERR_PLAN, "expressions read more than 16 columns");
         pcol[ci] = s.nprog_cols;
         s.prog_col[s.nprog_cols] = bound[ci]->data;
-        s.prog_col_type[s.nprog_cols] = bound[ci]->type;
+        s.prog_col_type[s.nprog_cols] = col_type(bound[ci]);
         s.nprog_cols++;
       }
       arg = pcol[ci];
@@ -658,8 +658,88 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
                        bool str_ok = false) -> nut_status {
       store.nodes.emplace_back();
       std::vector<nut_prog_node> &v = store.nodes.back();
+      // the temporal kind of every value on the program's stack, and where its nodes start
+      // in v: the calendar pseudo-nodes resolve against their operand's
+      struct KVal {
+        int kind;
+        size_t at;
+      };
+      std::vector<KVal> ks;
       for (const PNode &n : pp) {
-        nut_prog_node q{n.op, n.op == NUT_P_DATEPART ? n.arg : 0, 0};
+        const bool part = n.op == NUT_P_DATEPART || n.op == NUT_P_TIMEPART || n.op == NUT_P_DATETRUNC;
+        nut_prog_node q{n.op, part ? n.arg : 0, 0};
+        KVal a[3] = {{K_PLAIN, v.size()}, {K_PLAIN, v.size()}, {K_PLAIN, v.size()}};
+        const int ar = pnode_arity(n.op);
+        for (int i = ar - 1; i >= 0 && !ks.empty(); --i) a[i] = ks.back(), ks.pop_back();
+        int kind = K_PLAIN;
+        const size_t at = ar ? a[0].at : v.size();
+        auto done = [&]() { ks.push_back(KVal{kind, at}); };
+        if (n.op >= P_DAYS && n.op <= P_ADDIV) {
+          const nut_prog_node to_day{NUT_P_TIMEPART, NUT_TP_DATE, 0};
+          if (n.op == P_DAYS) {
+            if (a[0].kind == K_DATETIME) v.push_back(to_day);
+            kind = a[0].kind == K_DATETIME ? K_DATE : a[0].kind;
+          } else if (n.op == P_TODATE) {
+            if (a[0].kind != K_DATE) v.push_back(to_day);
+            kind = K_DATE;
+          } else if (n.op == P_SECS) {
+            if (a[0].kind == K_DATE)
+              return fail(NUT_ERR_PLAN, std::string(what) + ": '" + n.c.s + "' is a time function over a Date (it reads "
+                                        "seconds: a Datetime or an integer)");
+            kind = a[0].kind;
+          } else {  // P_ADDIV: x (from a[0].at), n (from a[1].at) on the stack
+            const int unit = n.arg & 7, xk = a[0].kind;
+            auto mul = [&](int64_t k) {
+              if (k == 1) return;
+              v.push_back(nut_prog_node{NUT_P_I64, 0, k});
+              v.push_back(nut_prog_node{NUT_P_MUL, 0, 0});
+            };
+            if (unit <= U_HOUR) {
+              if (xk == K_DATE || ((n.arg & kFromInterval) && xk != K_DATETIME))
+                return fail(NUT_ERR_PLAN, std::string(what) + ": '" + n.c.s + "': " +
+                                              ((n.arg & kFromInterval)
+                                                   ? "interval units below a day do not apply to day-number columns"
+                                                   : "a Date has no time of day (addSeconds / addMinutes / addHours take a "
+                                                     "Datetime or seconds)"));
+              mul(unit == U_SECOND ? 1 : unit == U_MINUTE ? 60 : 3600);
+              v.push_back(nut_prog_node{NUT_P_ADD, 0, 0});
+              kind = K_DATETIME;
+            } else if (unit <= U_WEEK) {
+              mul((unit == U_DAY ? 1 : 7) * (xk == K_DATETIME ? 86400ll : 1ll));
+              v.push_back(nut_prog_node{NUT_P_ADD, 0, 0});
+              kind = xk;
+            } else if (xk != K_DATETIME) {
+              mul(unit == U_MONTH ? 1 : unit == U_QUARTER ? 3 : 12);
+              v.push_back(nut_prog_node{NUT_P_ADDMONTHS, 0, 0});
+              kind = K_DATE;
+            } else {
+              // a Datetime: ADDMONTHS of its day, then its time of day back on
+              //   x DATE n*k ADDMONTHS 86400 * x x START_DAY - +
+              const std::vector<nut_prog_node> xs(v.begin() + (long)a[0].at, v.begin() + (long)a[1].at);
+              const std::vector<nut_prog_node> ns(v.begin() + (long)a[1].at, v.end());
+              v.resize(a[1].at);
+              v.push_back(to_day);
+              v.insert(v.end(), ns.begin(), ns.end());
+              mul(unit == U_MONTH ? 1 : unit == U_QUARTER ? 3 : 12);
+              v.push_back(nut_prog_node{NUT_P_ADDMONTHS, 0, 0});
+              mul(86400);
+              v.insert(v.end(), xs.begin(), xs.end());
+              v.insert(v.end(), xs.begin(), xs.end());
+              v.push_back(nut_prog_node{NUT_P_TIMEPART, NUT_TP_START_DAY, 0});
+              v.push_back(nut_prog_node{NUT_P_SUB, 0, 0});
+              v.push_back(nut_prog_node{NUT_P_ADD, 0, 0});
+              kind = K_DATETIME;
+            }
+          }
+          done();
+          continue;
+        }
+        if (n.op == NUT_P_COL) kind = col_kind(bound[n.col]);
+        else if (n.op == NUT_P_I64) kind = n.c.kind;
+        else if (n.op == NUT_P_TIMEPART) kind = n.arg >= NUT_TP_START_MINUTE && a[0].kind == K_DATETIME ? K_DATETIME : K_PLAIN;
+        else if (n.op == NUT_P_DATETRUNC || n.op == NUT_P_ADDMONTHS) kind = K_DATE;
+        else if (n.op == NUT_P_IF) kind = a[1].kind == a[2].kind ? a[1].kind : K_PLAIN;
+        done();
         if (n.op == P_LIKE || n.op == P_ILIKE) {
           nut_status ls = lower_like(n, v);
           if (ls) return ls;
@@ -679,7 +759,7 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
             if (s.nprog_cols >= NUT_MAX_PROG_COLS) return fail(NUT_ERR_PLAN, "expressions read more than 16 columns");
             pcol[n.col] = s.nprog_cols;
             s.prog_col[s.nprog_cols] = bound[n.col]->data;
-            s.prog_col_type[s.nprog_cols] = bound[n.col]->type;
+            s.prog_col_type[s.nprog_cols] = col_type(bound[n.col]);
             s.nprog_cols++;
           }
           q.arg = pcol[n.col];
@@ -789,7 +869,7 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
         // constant never equals an int64)
         std::vector<int64_t> vals;
         for (const CVal &v : pr.set) {
-          if (col->type == NUT_T_I64) {
+          if (col_type(col) == NUT_T_I64) {
             int o2;
             int64_t k;
             if (resolve_i64(NUT_EQ, v, o2, k) == V_PRED) vals.push_back(k);
@@ -805,14 +885,14 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
           continue;
         }
         s.pred_col[s.npred] = col->data;
-        s.pred_type[s.npred] = col->type;
+        s.pred_type[s.npred] = col_type(col);
         s.pred_op[s.npred] = pr.op;
         s.pred_nset[s.npred] = (int32_t)vals.size();
         for (size_t j = 0; j < vals.size(); ++j) s.pred_set[s.npred][j] = vals[j];
         s.npred++;
         continue;
       }
-      if (col->type == NUT_T_I64) {
+      if (col_type(col) == NUT_T_I64) {
         int op;
         int64_t k;
         Verdict v = resolve_i64(pr.op, pr.c, op, k);
@@ -838,7 +918,7 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
       if (dicts && dicts[p.vals[v]])
         return fail(NUT_ERR_PLAN, "aggregate over the string column '" + p.cols[p.vals[v]] + "' (only count)");
       s.val_col[v] = bound[p.vals[v]]->data;
-      s.val_type[v] = bound[p.vals[v]]->type;
+      s.val_type[v] = col_type(bound[p.vals[v]]);
     }
     s.naggs = (int32_t)p.aggs.size();
     for (size_t a = 0; a < p.aggs.size(); ++a) {

@@ -10,7 +10,9 @@
 //     bound (x < 2.5 -> x <= 2) and an out-of-range constant folds to true/false.
 //   * constants: Literal::Integer(u128, sign) and Literal::Float(BigDecimal) (exact,
 //     converted with correct rounding for f64 columns), toDate('YYYY-MM-DD') and
-//     date +/- interval n day|month|year, as days since 1970-01-01.
+//     date +/- interval n day|month|year, as days since 1970-01-01;
+//     toDateTime('YYYY-MM-DD hh:mm:ss') as seconds; every calendar function of constants
+//     (const_eval, with the host twins of the device functions: DESIGN.md §3.12).
 //   * SELECT-list FnCall Others(name): sum/count/min/max/avg, case-insensitive
 //     (the parser keeps the original case, mod.rs:1305); count(*) is the wildcard
 //     Identifier (mod.rs:1271); avg = sum / count.  Arguments: a column or one of the
@@ -100,6 +102,11 @@ void civil_from_days(int64_t z, int64_t &y, unsigned &m, unsigned &d) {
   y += m <= 2;
 }
 bool leap(int64_t y) { return (y % 4 == 0 && y % 100 != 0) || y % 400 == 0; }
+// floor division / modulo by a positive g, and the operand clamps of the calendar ops
+int64_t floor_div(int64_t a, int64_t g) { return a / g - (a % g < 0 ? 1 : 0); }
+int64_t floor_mod(int64_t a, int64_t g) { return a - floor_div(a, g) * g; }
+int64_t clamp64(int64_t x, int64_t m) { return std::max(-m, std::min(m, x)); }
+int64_t sat64(i128 v) { return v > INT64_MAX ? INT64_MAX : v < INT64_MIN ? INT64_MIN : (int64_t)v; }
 // nut_date_part of a day number (the DATEPART program op's host twin, for constants)
 int64_t date_part(int64_t d, int part) {
   d = std::max<int64_t>(-(1ll << 40), std::min<int64_t>(1ll << 40, d));
@@ -114,6 +121,9 @@ int64_t date_part(int64_t d, int part) {
     case NUT_DP_WEEKDAY: return ((d % 7 + 7) % 7 + 3) % 7 + 1;
     case NUT_DP_YYYYMM: return y * 100 + m;
     case NUT_DP_YYYYMMDD: return y * 10000 + m * 100 + dd;
+    case NUT_DP_REL_MONTH: return y * 12 + m;
+    case NUT_DP_REL_QUARTER: return y * 4 + (m - 1) / 3;
+    case NUT_DP_REL_WEEK: return floor_div(d + 3, 7);
     default: return d - days_from_civil(y, 1, 1) + 1;
   }
 }
@@ -123,8 +133,11 @@ int date_fn(sv n) {
   static const char *const names[][2] = {{"toyear", "getyear"},         {"tomonth", "getmonth"},
                                           {"todayofmonth", "getdayofmonth"}, {"toquarter", "getquarter"},
                                           {"todayofweek", "getdayofweek"}, {"todayofyear", "getdayofyear"},
-                                          {"toyyyymm", "toyyyymm"},         {"toyyyymmdd", "toyyyymmdd"}};
-  for (int i = 0; i < 8; ++i)
+                                          {"toyyyymm", "toyyyymm"},         {"toyyyymmdd", "toyyyymmdd"},
+                                          {"torelativemonthnum", "torelativemonthnum"},
+                                          {"torelativequarternum", "torelativequarternum"},
+                                          {"torelativeweeknum", "torelativeweeknum"}};
+  for (int i = 0; i < 11; ++i)
     if (ieq(n, names[i][0]) || ieq(n, names[i][1])) return i;
   return -1;
 }
@@ -162,6 +175,161 @@ int64_t add_months(int64_t days, i128 months) {
   return days_from_civil(ny, nm, nd);
 }
 
+// host twins of the TIMEPART / DATETRUNC / ADDMONTHS program ops (jit.cpp: jtimepart,
+// jdatetrunc, jaddmonths), clamps included
+int64_t time_part(int64_t s, int part) {
+  s = clamp64(s, (1ll << 40) * 86400);
+  static const int64_t g[] = {60, 300, 900, 3600, 86400};
+  switch (part) {
+    case NUT_TP_DATE: return floor_div(s, 86400);
+    case NUT_TP_HOUR: return floor_mod(s, 86400) / 3600;
+    case NUT_TP_MINUTE: return floor_mod(s, 3600) / 60;
+    case NUT_TP_SECOND: return floor_mod(s, 60);
+    default: return s - floor_mod(s, g[part - NUT_TP_START_MINUTE]);
+  }
+}
+int64_t date_trunc(int64_t d, int unit) {
+  d = clamp64(d, 1ll << 40);
+  if (unit == NUT_DT_WEEK_MONDAY) return d - floor_mod(d + 3, 7);
+  if (unit == NUT_DT_WEEK_SUNDAY) return d - floor_mod(d + 4, 7);
+  int64_t y;
+  unsigned m, dd;
+  civil_from_days(d, y, m, dd);
+  switch (unit) {
+    case NUT_DT_MONTH: return days_from_civil(y, m, 1);
+    case NUT_DT_QUARTER: return days_from_civil(y, (m - 1) / 3 * 3 + 1, 1);
+    case NUT_DT_YEAR: return days_from_civil(y, 1, 1);
+    default: return days_from_civil(y, m, month_days(y, m));
+  }
+}
+int64_t add_months_op(int64_t d, int64_t n) { return add_months(clamp64(d, 1ll << 40), clamp64(n, 1ll << 36)); }
+
+namespace {
+int64_t wadd(int64_t a, int64_t b) { return (int64_t)((uint64_t)a + (uint64_t)b); }
+int64_t wsub(int64_t a, int64_t b) { return (int64_t)((uint64_t)a - (uint64_t)b); }
+int64_t wmul(int64_t a, int64_t b) { return (int64_t)((uint64_t)a * (uint64_t)b); }
+
+// Calendar functions beyond date_fn.  cls 0: TIMEPART (arg = nut_time_part); 1: DATETRUNC
+// (arg = nut_date_trunc); 2: addX / subtractX (arg = TUnit)
+struct CalFn {
+  int cls = -1, arg = 0;
+  bool neg = false;
+};
+const char *const kUnitNames[] = {"second", "minute", "hour", "day", "week", "month", "quarter", "year"};
+const char *const kAddNames[] = {"addSeconds", "addMinutes", "addHours", "addDays",
+                                 "addWeeks",   "addMonths",  "addQuarters", "addYears"};
+const char *const kTimePartNames[] = {"toDate", "toHour", "toMinute", "toSecond", "toStartOfMinute",
+                                      "toStartOfFiveMinutes", "toStartOfFifteenMinutes", "toStartOfHour", "toStartOfDay"};
+const char *const kDateTruncNames[] = {"toMonday", "toStartOfWeek", "toStartOfMonth", "toStartOfQuarter",
+                                       "toStartOfYear", "toLastDayOfMonth"};
+bool cal_fn(sv n, CalFn &f) {
+  static const struct {
+    const char *a, *b;
+    int cls, arg;
+  } t[] = {{"tohour", "gethour", 0, NUT_TP_HOUR},
+           {"tominute", "getminute", 0, NUT_TP_MINUTE},
+           {"tosecond", "getsecond", 0, NUT_TP_SECOND},
+           {"tostartofminute", "", 0, NUT_TP_START_MINUTE},
+           {"tostartoffiveminutes", "tostartoffiveminute", 0, NUT_TP_START_FIVE_MINUTES},
+           {"tostartoffifteenminutes", "", 0, NUT_TP_START_FIFTEEN_MINUTES},
+           {"tostartofhour", "", 0, NUT_TP_START_HOUR},
+           {"tostartofday", "", 0, NUT_TP_START_DAY},
+           {"tomonday", "", 1, NUT_DT_WEEK_MONDAY},
+           {"tostartofweek", "", 1, NUT_DT_WEEK_SUNDAY},
+           {"tostartofmonth", "", 1, NUT_DT_MONTH},
+           {"tostartofquarter", "", 1, NUT_DT_QUARTER},
+           {"tostartofyear", "", 1, NUT_DT_YEAR},
+           {"tolastdayofmonth", "", 1, NUT_DT_MONTH_END}};
+  for (const auto &x : t)
+    if (ieq(n, x.a) || (*x.b && ieq(n, x.b))) {
+      f.cls = x.cls, f.arg = x.arg;
+      return true;
+    }
+  for (int neg = 0; neg < 2; ++neg)
+    for (int u = 0; u < 8; ++u)
+      if (ieq(n, std::string(neg ? "subtract" : "add") + kUnitNames[u] + "s")) {
+        f.cls = 2, f.arg = u, f.neg = neg != 0;
+        return true;
+      }
+  return false;
+}
+int unit_of(sv n) {
+  for (int u = 0; u < 8; ++u)
+    if (ieq(n, kUnitNames[u])) return u;
+  return -1;
+}
+int unit_of(IntervalUnit u) {
+  switch (u) {
+    case IntervalUnit::Second: return U_SECOND;
+    case IntervalUnit::Minute: return U_MINUTE;
+    case IntervalUnit::Hour: return U_HOUR;
+    case IntervalUnit::Day: return U_DAY;
+    case IntervalUnit::Month: return U_MONTH;
+    default: return U_YEAR;
+  }
+}
+const char *const kSubDayInterval = "interval units below a day do not apply to day-number columns";
+const char *const kSubDayDate = "a Date has no time of day (addSeconds / addMinutes / addHours take a Datetime or seconds)";
+
+// x (of kind `kind`) plus n units, as the program build_spec emits for P_ADDIV computes it
+// (wrapping + and *, the ops' clamps).  false: the unit does not apply to the kind (err).
+bool add_units(int64_t x, int kind, int unit, int64_t n, bool from_interval, int64_t &out, int &okind,
+               std::string &err) {
+  if (unit <= U_HOUR) {
+    if (kind == K_DATE || (from_interval && kind != K_DATETIME)) {
+      err = from_interval ? kSubDayInterval : kSubDayDate;
+      return false;
+    }
+    out = wadd(x, wmul(n, unit == U_SECOND ? 1 : unit == U_MINUTE ? 60 : 3600));
+    okind = K_DATETIME;
+  } else if (unit <= U_WEEK) {
+    out = wadd(x, wmul(n, (unit == U_DAY ? 1 : 7) * (kind == K_DATETIME ? 86400ll : 1ll)));
+    okind = kind;
+  } else {
+    const int64_t mo = wmul(n, unit == U_MONTH ? 1 : unit == U_QUARTER ? 3 : 12);
+    if (kind == K_DATETIME) {
+      out = wadd(wmul(add_months_op(time_part(x, NUT_TP_DATE), mo), 86400), wsub(x, time_part(x, NUT_TP_START_DAY)));
+      okind = K_DATETIME;
+    } else {
+      out = add_months_op(x, mo);
+      okind = K_DATE;
+    }
+  }
+  return true;
+}
+// dateDiff's f: the number of `unit` boundaries before x
+bool diff_count(int64_t x, int kind, int unit, int64_t &out) {
+  if (unit <= U_HOUR) {
+    if (kind == K_DATE) return false;
+    out = unit == U_SECOND ? x : floor_div(clamp64(x, (1ll << 40) * 86400), unit == U_MINUTE ? 60 : 3600);
+    return true;
+  }
+  const int64_t d = kind == K_DATETIME ? time_part(x, NUT_TP_DATE) : x;
+  out = unit == U_DAY ? d : date_part(d, unit == U_WEEK ? NUT_DP_REL_WEEK : unit == U_MONTH ? NUT_DP_REL_MONTH
+                                         : unit == U_QUARTER ? NUT_DP_REL_QUARTER : NUT_DP_YEAR);
+  return true;
+}
+// 'YYYY-MM-DD hh:mm:ss' -> seconds since 1970-01-01 00:00:00
+bool parse_datetime(sv s, int64_t &secs) {
+  if (s.size() != 19 || (s[10] != ' ' && s[10] != 'T') || s[13] != ':' || s[16] != ':') return false;
+  int64_t days;
+  if (!parse_date(s.substr(0, 10), days)) return false;
+  int v[3];
+  for (int k = 0; k < 3; ++k) {
+    const char a = s[11 + 3 * k], b = s[12 + 3 * k];
+    if (a < '0' || a > '9' || b < '0' || b > '9') return false;
+    v[k] = (a - '0') * 10 + (b - '0');
+  }
+  if (v[0] > 23 || v[1] > 59 || v[2] > 59) return false;
+  secs = days * 86400 + v[0] * 3600 + v[1] * 60 + v[2];
+  return true;
+}
+// an integer constant argument (no string, no subquery placeholder)
+bool const_int(const Expr &e, CVal &x, Lowering &L) {
+  return const_eval(e, x, L) && x.is_int && !x.is_str && x.param < 0;
+}
+}  // namespace
+
 
 bool const_eval(const Expr &e, CVal &out, Lowering &L) {
   if (e.k == EK::Literal) {
@@ -190,14 +358,85 @@ bool const_eval(const Expr &e, CVal &out, Lowering &L) {
     if (!parse_date(e.kids[0].lit->str, days)) return L.fail("toDate: '" + e.kids[0].lit->str + "' is not YYYY-MM-DD");
     out.is_int = true;
     out.v = days;
+    out.kind = K_DATE;
+    return true;
+  }
+  if (e.k == EK::FnCall && e.fn() == FnKind::Others && ieq(e.id.name, "todatetime")) {
+    int64_t secs;
+    if (e.kids.size() != 1 || e.kids[0].k != EK::Literal || e.kids[0].lit->k != LitKind::String)
+      return L.fail("toDateTime takes one 'YYYY-MM-DD hh:mm:ss' constant");
+    if (!parse_datetime(e.kids[0].lit->str, secs))
+      return L.fail("toDateTime: '" + e.kids[0].lit->str + "' is not YYYY-MM-DD hh:mm:ss");
+    out.is_int = true;
+    out.v = secs;
+    out.kind = K_DATETIME;
     return true;
   }
   if (e.k == EK::FnCall && e.fn() == FnKind::Others && date_fn(e.id.name) >= 0 && e.kids.size() == 1) {
     CVal x;
     if (!const_eval(e.kids[0], x, L) || !x.is_int || x.is_str) return false;
     out.is_int = true;
-    out.v = date_part((int64_t)std::max<i128>(-(i128(1) << 41), std::min<i128>(i128(1) << 41, x.v)), date_fn(e.id.name));
+    // (a Datetime constant: its day first)
+    const int64_t d = x.kind == K_DATETIME ? time_part(sat64(x.v), NUT_TP_DATE)
+                                           : (int64_t)std::max<i128>(-(i128(1) << 41), std::min<i128>(i128(1) << 41, x.v));
+    out.v = date_part(d, date_fn(e.id.name));
     return true;
+  }
+  if (e.k == EK::FnCall && e.fn() == FnKind::Others) {  // the other calendar functions of constants
+    const sv n = e.id.name;
+    const size_t na = e.kids.size();
+    CalFn cf;
+    CVal x, y;
+    if (ieq(n, "todate") && na == 1) {
+      if (!const_int(e.kids[0], x, L)) return false;
+      out = CVal{};
+      out.v = x.kind == K_DATE ? x.v : (i128)time_part(sat64(x.v), NUT_TP_DATE);
+      out.kind = K_DATE;
+      return true;
+    }
+    if (cal_fn(n, cf) && cf.cls == 0 && na == 1) {
+      if (!const_int(e.kids[0], x, L)) return false;
+      if (x.kind == K_DATE) return L.fail("'" + expr_text(e) + "': a time function over a Date (it reads seconds)");
+      out = CVal{};
+      out.v = time_part(sat64(x.v), cf.arg);
+      out.kind = cf.arg >= NUT_TP_START_MINUTE && x.kind == K_DATETIME ? K_DATETIME : K_PLAIN;
+      return true;
+    }
+    if (cal_fn(n, cf) && cf.cls == 1 && (na == 1 || (na == 2 && ieq(n, "tostartofweek")))) {
+      if (!const_int(e.kids[0], x, L)) return false;
+      int unit = cf.arg;
+      if (na == 2) {
+        if (!const_int(e.kids[1], y, L) || (y.v != 0 && y.v != 1)) return L.fail("toStartOfWeek: the mode is 0 (Sunday) or 1 (Monday)");
+        unit = y.v == 1 ? NUT_DT_WEEK_MONDAY : NUT_DT_WEEK_SUNDAY;
+      }
+      out = CVal{};
+      out.v = date_trunc(x.kind == K_DATETIME ? time_part(sat64(x.v), NUT_TP_DATE) : sat64(x.v), unit);
+      out.kind = K_DATE;
+      return true;
+    }
+    if (cal_fn(n, cf) && cf.cls == 2 && na == 2) {
+      if (!const_int(e.kids[0], x, L) || !const_int(e.kids[1], y, L)) return false;
+      int64_t r;
+      int k;
+      std::string err;
+      const int64_t cnt = cf.neg ? wsub(0, sat64(y.v)) : sat64(y.v);
+      if (!add_units(sat64(x.v), x.kind, cf.arg, cnt, false, r, k, err)) return L.fail("'" + expr_text(e) + "': " + err);
+      out = CVal{};
+      out.v = r;
+      out.kind = k;
+      return true;
+    }
+    if (ieq(n, "datediff") && na == 3 && e.kids[0].k == EK::Literal && e.kids[0].lit->k == LitKind::String) {
+      const int unit = unit_of(e.kids[0].lit->str);
+      if (unit < 0) return L.fail("dateDiff: unit '" + e.kids[0].lit->str + "' (second, minute, hour, day, week, month, quarter, year)");
+      if (!const_int(e.kids[1], x, L) || !const_int(e.kids[2], y, L)) return false;
+      int64_t fa, fb;
+      if (!diff_count(sat64(x.v), x.kind, unit, fa) || !diff_count(sat64(y.v), y.kind, unit, fb))
+        return L.fail("'" + expr_text(e) + "': a unit below a day over a Date (it reads seconds)");
+      out = CVal{};
+      out.v = wsub(fb, fa);
+      return true;
+    }
   }
   if (e.k == EK::BinaryOp && (e.bop() == BinOp::Plus || e.bop() == BinOp::Minus)) {
     const Expr &a = e.kids[0], &b = e.kids[1];
@@ -207,6 +446,16 @@ bool const_eval(const Expr &e, CVal &out, Lowering &L) {
       if (!const_eval(a, x, L) || !x.is_int) return false;
       const i128 n = sign * (i128)b.lit->interval;
       if (x.v > INT64_MAX || x.v < INT64_MIN) return false;
+      out.kind = x.kind;
+      if (x.kind == K_DATETIME) {  // seconds: every unit applies
+        int64_t r;
+        int k;
+        std::string err;
+        add_units((int64_t)x.v, K_DATETIME, unit_of(b.lit->unit), sat64(n), true, r, k, err);
+        out.v = r;
+        out.is_int = true;
+        return true;
+      }
       switch (b.lit->unit) {
         case IntervalUnit::Day: out.v = x.v + n; break;
         case IntervalUnit::Month: out.v = add_months((int64_t)x.v, n); break;
@@ -267,8 +516,10 @@ int mirror(int op) { return op == NUT_LT ? NUT_GT : op == NUT_GT ? NUT_LT : op =
 
 int pnode_arity(int op) {
   if (op == P_LIKE || op == P_ILIKE || op == P_SUBSTR) return 0;
-  return op <= NUT_P_F64 ? 0 : (op == NUT_P_NOT || op == NUT_P_BITNOT || op == NUT_P_ABS ||
-                                op == NUT_P_TO_F64 || op == NUT_P_DATEPART) ? 1 : op == NUT_P_IF ? 3 : 2;
+  if (op == P_DAYS || op == P_SECS || op == P_TODATE) return 1;
+  return op <= NUT_P_F64 ? 0 : (op == NUT_P_NOT || op == NUT_P_BITNOT || op == NUT_P_ABS || op == NUT_P_TO_F64 ||
+                                op == NUT_P_DATEPART || op == NUT_P_TIMEPART || op == NUT_P_DATETRUNC) ? 1
+                               : op == NUT_P_IF ? 3 : 2;
 }
 
 // bytes of the UTF-8 sequence starting at s[i] (a stray continuation byte counts alone)
@@ -669,6 +920,17 @@ bool lower_prog(nut_plan &p, const Expr &e, PProg &o, Lowering &L) {
         if (b == BinOp::NotLike || b == BinOp::NotILike) emit(o, NUT_P_NOT);
         return true;
       }
+      if ((b == BinOp::Plus || b == BinOp::Minus) && e.kids[1].k == EK::Literal && e.kids[1].lit->k == LitKind::Interval) {
+        // x +/- interval n unit over a column expression: the kind of x decides the arithmetic
+        if (!lower_prog(p, e.kids[0], o, L)) return false;
+        emit_int(o, (b == BinOp::Plus ? 1 : -1) * (i128)e.kids[1].lit->interval);
+        PNode ai;
+        ai.op = P_ADDIV;
+        ai.arg = unit_of(e.kids[1].lit->unit) | kFromInterval;
+        ai.c.s = expr_text(e);
+        o.push_back(ai);
+        return true;
+      }
       const int op = prog_binop(b);
       if (op < 0) return L.fail("operator in '" + expr_text(e) + "' is not executed ([] and friends)");
       PProg l, r;
@@ -733,12 +995,86 @@ bool lower_prog(nut_plan &p, const Expr &e, PProg &o, Lowering &L) {
         emit(o, ieq(n, "intdiv") ? NUT_P_INTDIV : NUT_P_MOD);
         return true;
       }
+      auto node = [&](int op, int arg) {
+        PNode x;
+        x.op = op;
+        x.arg = arg;
+        if (op >= P_DAYS) x.c.s = expr_text(e);
+        o.push_back(x);
+      };
       if (date_fn(n) >= 0 && na == 1) {
         if (!lower_prog(p, e.kids[0], o, L)) return false;
-        PNode dp;
-        dp.op = NUT_P_DATEPART;
-        dp.arg = date_fn(n);
-        o.push_back(dp);
+        node(P_DAYS, 0);  // (a Datetime operand: its day number)
+        node(NUT_P_DATEPART, date_fn(n));
+        return true;
+      }
+      CalFn cf;
+      if (cal_fn(n, cf) && cf.cls == 0 && na == 1) {
+        if (!lower_prog(p, e.kids[0], o, L)) return false;
+        node(P_SECS, 0);  // (a Date operand: a plan error at execution)
+        node(NUT_P_TIMEPART, cf.arg);
+        return true;
+      }
+      if (cal_fn(n, cf) && cf.cls == 1 && (na == 1 || (na == 2 && ieq(n, "tostartofweek")))) {
+        int unit = cf.arg;
+        if (na == 2) {
+          CVal mode;
+          if (!const_int(e.kids[1], mode, L) || (mode.v != 0 && mode.v != 1))
+            return L.fail("toStartOfWeek: the mode is the constant 0 (Sunday) or 1 (Monday)");
+          unit = mode.v == 1 ? NUT_DT_WEEK_MONDAY : NUT_DT_WEEK_SUNDAY;
+        }
+        if (!lower_prog(p, e.kids[0], o, L)) return false;
+        node(P_DAYS, 0);
+        node(NUT_P_DATETRUNC, unit);
+        return true;
+      }
+      if (cal_fn(n, cf) && cf.cls == 2 && na == 2) {
+        if (!lower_prog(p, e.kids[0], o, L)) return false;
+        if (cf.neg) emit_int(o, 0);
+        if (!lower_prog(p, e.kids[1], o, L)) return false;
+        if (cf.neg) emit(o, NUT_P_SUB);  // subtractX(x, n) = addX(x, 0 - n)
+        node(P_ADDIV, cf.arg);
+        return true;
+      }
+      if (ieq(n, "todate") && na == 1) {
+        if (!lower_prog(p, e.kids[0], o, L)) return false;
+        node(P_TODATE, 0);
+        return true;
+      }
+      if (ieq(n, "datediff") && na == 3) {
+        if (e.kids[0].k != EK::Literal || e.kids[0].lit->k != LitKind::String || unit_of(e.kids[0].lit->str) < 0)
+          return L.fail("dateDiff takes a unit ('second', 'minute', 'hour', 'day', 'week', 'month', 'quarter', 'year') "
+                        "and two values");
+        const int unit = unit_of(e.kids[0].lit->str);
+        // f(b) - f(a), f = the unit boundaries before its operand (literal divisors only)
+        for (int side = 2; side >= 1; --side) {
+          PProg x;
+          if (!lower_prog(p, e.kids[side], x, L)) return false;
+          auto put = [&](int op, int arg) {
+            append(o, x);
+            node(unit <= U_HOUR ? P_SECS : P_DAYS, 0);
+            if (op) node(op, arg);
+          };
+          if (unit == U_SECOND || unit == U_DAY) {
+            put(0, 0);
+          } else if (unit == U_HOUR || unit == U_MINUTE) {  // day * 24 + hour [, * 60 + minute]
+            put(NUT_P_TIMEPART, NUT_TP_DATE);
+            emit_int(o, 24);
+            emit(o, NUT_P_MUL);
+            put(NUT_P_TIMEPART, NUT_TP_HOUR);
+            emit(o, NUT_P_ADD);
+            if (unit == U_MINUTE) {
+              emit_int(o, 60);
+              emit(o, NUT_P_MUL);
+              put(NUT_P_TIMEPART, NUT_TP_MINUTE);
+              emit(o, NUT_P_ADD);
+            }
+          } else {
+            put(NUT_P_DATEPART, unit == U_WEEK ? NUT_DP_REL_WEEK : unit == U_MONTH ? NUT_DP_REL_MONTH
+                                : unit == U_QUARTER ? NUT_DP_REL_QUARTER : NUT_DP_YEAR);
+          }
+        }
+        emit(o, NUT_P_SUB);
         return true;
       }
       if ((ieq(n, "substring") || ieq(n, "substr") || ieq(n, "mid")) && (na == 2 || na == 3)) {
@@ -759,10 +1095,12 @@ bool lower_prog(nut_plan &p, const Expr &e, PProg &o, Lowering &L) {
         o.push_back(sn);
         return true;
       }
-      if (ieq(n, "todate")) return L.fail("toDate takes one 'YYYY-MM-DD' constant");
+      if (ieq(n, "todate")) return L.fail("toDate takes one 'YYYY-MM-DD' constant or one expression");
       return L.fail("function '" + std::string(n) + "' is not executed (executed: if, multiIf, abs, toFloat64, intDiv, "
                     "modulo, substring, toYear/getYear, toMonth, toDayOfMonth, toQuarter, toDayOfWeek, toDayOfYear, toYYYYMM, "
-                    "toYYYYMMDD)");
+                    "toYYYYMMDD, toRelativeMonthNum / QuarterNum / WeekNum, toHour, toMinute, toSecond, toDate, toDateTime, "
+                    "toStartOfMinute / FiveMinutes / FifteenMinutes / Hour / Day / Week / Month / Quarter / Year, toMonday, "
+                    "toLastDayOfMonth, add / subtract Seconds .. Years, dateDiff)");
     }
     default: return L.fail("'" + expr_text(e) + "' is not executed (parameters, collections, subqueries)");
   }
@@ -2042,8 +2380,22 @@ std::string prog_text(const nut_plan &p, const PProg &pp) {
     else if (n.op == NUT_P_I64 || n.op == NUT_P_F64) st.push_back(cval_str(n.c));
     else if (n.op == NUT_P_DATEPART) {
       static const char *dp[] = {"toYear",      "toMonth",     "toDayOfMonth", "toQuarter",
-                                 "toDayOfWeek", "toDayOfYear", "toYYYYMM",     "toYYYYMMDD"};
-      st.push_back(std::string(n.arg >= 0 && n.arg < 8 ? dp[n.arg] : "datepart") + "(" + pop() + ")");
+                                 "toDayOfWeek", "toDayOfYear", "toYYYYMM",     "toYYYYMMDD",
+                                 "toRelativeMonthNum", "toRelativeQuarterNum", "toRelativeWeekNum"};
+      st.push_back(std::string(n.arg >= 0 && n.arg < 11 ? dp[n.arg] : "datepart") + "(" + pop() + ")");
+    } else if (n.op == P_DAYS || n.op == P_SECS) {
+      // (the operand as the function reads it: shown as written)
+    } else if (n.op == P_TODATE) {
+      st.push_back("toDate(" + pop() + ")");
+    } else if (n.op == NUT_P_TIMEPART) {
+      st.push_back(std::string(n.arg >= 0 && n.arg < 9 ? kTimePartNames[n.arg] : "timepart") + "(" + pop() + ")");
+    } else if (n.op == NUT_P_DATETRUNC) {
+      const std::string x = pop();
+      st.push_back(n.arg == NUT_DT_WEEK_SUNDAY ? "toStartOfWeek(" + x + ", 0)"
+                                               : std::string(n.arg >= 0 && n.arg < 6 ? kDateTruncNames[n.arg] : "datetrunc") + "(" + x + ")");
+    } else if (n.op == NUT_P_ADDMONTHS || n.op == P_ADDIV) {
+      std::string r = pop(), l = pop();
+      st.push_back(std::string(n.op == P_ADDIV ? kAddNames[n.arg & 7] : "addMonths") + "(" + l + ", " + r + ")");
     } else if (n.op == NUT_P_NOT || n.op == NUT_P_BITNOT || n.op == NUT_P_ABS || n.op == NUT_P_TO_F64) {
       const char *f = n.op == NUT_P_NOT ? "not" : n.op == NUT_P_BITNOT ? "~" : n.op == NUT_P_ABS ? "abs" : "toFloat64";
       st.push_back(std::string(f) + "(" + pop() + ")");

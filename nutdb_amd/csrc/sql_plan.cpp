@@ -5,6 +5,11 @@
 
 namespace {
 
+// a typed table's Date / Datetime column tells the calendar functions its kind
+int table_kind_flag(const TCol &c) {
+  return c.kind == NUT_COL_DATE ? NUT_COL_AS_DATE : c.kind == NUT_COL_DATETIME ? NUT_COL_AS_DATETIME : 0;
+}
+
 // exact decimal of a finite double (17 significant digits: strtod gives the double back)
 Decimal decimal_of(double d) {
   Decimal x;
@@ -325,7 +330,7 @@ nut_status nut_plan_route(const nut_plan *p, const nut_column *cols, int ncols, 
   for (size_t i = 0; i < p->cols.size(); ++i) {
     bound[i] = bind(*p, (int)i, cols, ncols);
     if (!bound[i]) return fail(NUT_ERR_INVALID_ARG, "nut_plan_route: column '" + p->cols[i] + "' is not bound");
-    if (!type_known(bound[i]->type))
+    if (!type_known(col_type(bound[i])))
       return fail(NUT_ERR_INVALID_ARG, "nut_plan_route: column '" + p->cols[i] + "' has an unknown type");
   }
   std::string route;
@@ -340,7 +345,7 @@ nut_status nut_plan_route(const nut_plan *p, const nut_column *cols, int ncols, 
     std::deque<nut_column> words;
     int nf = 0;
     for (int k : p->keys)
-      if (k >= 0 && type_is_float(bound[k]->type)) {
+      if (k >= 0 && type_is_float(col_type(bound[k]))) {
         words.push_back(nut_column{bound[k]->name, nullptr, NUT_T_I64});
         bound[k] = &words.back();
         ++nf;
@@ -419,7 +424,7 @@ nut_status nut_plan_execute(nut_ctx *c, const nut_plan *p, const nut_column *col
   for (size_t i = 0; i < p->cols.size(); ++i) {
     bound[i] = bind(*p, (int)i, cols, ncols);
     if (!bound[i]) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: column '" + p->cols[i] + "' is not bound");
-    if (!type_known(bound[i]->type))
+    if (!type_known(col_type(bound[i])))
       return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: column '" + p->cols[i] + "' has an unknown type");
     if (nrows && !bound[i]->data) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: column '" + p->cols[i] + "' is NULL");
   }
@@ -571,7 +576,7 @@ nut_status nut_plan_prepare(const nut_plan *p, const nut_column *cols, int ncols
   if (!p->uni.empty()) return NUT_OK;
   bool any_narrow = false;
   for (int i = 0; i < ncols; ++i) {
-    const int t = cols[i].type & ~NUT_COL_HOST;
+    const int t = col_type(&cols[i]) & ~NUT_COL_HOST;
     any_narrow = any_narrow || (type_known(t) && type_width(t) < 8);
   }
   if (!p->compiled && !(any_narrow && p->kind == NUT_PLAN_GROUPBY)) return NUT_OK;  // precompiled kernels only
@@ -593,7 +598,7 @@ nut_status nut_plan_prepare(const nut_plan *p, const nut_column *cols, int ncols
     typed[i] = *bound[i];
     typed[i].type &= ~NUT_COL_HOST;  // only the type matters here
     bound[i] = &typed[i];
-    if (!type_known(bound[i]->type))
+    if (!type_known(col_type(bound[i])))
       return fail(NUT_ERR_INVALID_ARG, "nut_plan_prepare: column '" + p->cols[i] + "' has an unknown type");
   }
   nut_plan nq;  // narrow columns: the expression-mode plan that executes (a Float32 key is widened there)
@@ -675,7 +680,7 @@ nut_status nut_table_execute(nut_ctx *c, nut_table *t, const nut_plan *p, uint64
     for (const TCol &x : t->cols)
       if (!tc && dot != std::string::npos && ieq(x.name, sv(p->cols[i]).substr(dot + 1))) tc = &x;
     if (!tc) return fail(NUT_ERR_PLAN, "table '" + t->name + "' has no column '" + p->cols[i] + "'");
-    cols[i] = nut_column{tc->name.c_str(), tc->dev, tc->exec_type};
+    cols[i] = nut_column{tc->name.c_str(), tc->dev, tc->exec_type | table_kind_flag(*tc)};
     bound[i] = &cols[i];
     dicts[i] = ov.of(tc->dict);
   }
@@ -730,7 +735,7 @@ nut_status nut_table_execute2(nut_ctx *c, nut_table *left, nut_table *right, con
     if (t->device >= 0 && t->device != c->device)
       return fail(NUT_ERR_INVALID_ARG, "nut_table_execute2: table '" + t->name + "' lives on another device");
     for (const TCol &x : t->cols) {
-      cols[k].push_back(nut_column{x.name.c_str(), x.dev, x.exec_type});
+      cols[k].push_back(nut_column{x.name.c_str(), x.dev, x.exec_type | table_kind_flag(x)});
       dicts[k].push_back(ov.of(x.dict));
     }
   }
@@ -803,7 +808,7 @@ nut_status nut_table_executen(nut_ctx *c, nut_table *const *tables, int ntables,
     if (t->device >= 0 && t->device != c->device)
       return fail(NUT_ERR_INVALID_ARG, "nut_table_executen: table '" + t->name + "' lives on another device");
     for (const TCol &x : t->cols) {
-      cols[k].push_back(nut_column{x.name.c_str(), x.dev, x.exec_type});
+      cols[k].push_back(nut_column{x.name.c_str(), x.dev, x.exec_type | table_kind_flag(x)});
       dicts[k].push_back(ov.of(x.dict));
     }
     tabs[k] = cols[k].data();

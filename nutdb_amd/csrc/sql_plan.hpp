@@ -39,7 +39,14 @@ struct CVal {
   bool is_str = false;  // string constant (binds to a dictionary code at execution)
   std::string s;
   int param = -1;       // >= 0: the value of scalar subquery nut_plan.subs[param], known at execution
+  int kind = 0;         // TKind of an integer constant (toDate(..): K_DATE, toDateTime(..): K_DATETIME)
 };
+// The temporal kind of an expression.  Programs are untyped int64; the
+// kind says what a calendar function reads: day numbers, seconds, or a plain integer (day
+// functions read it as days, time functions as seconds).
+enum TKind { K_PLAIN = 0, K_DATE = 1, K_DATETIME = 2 };
+// units of addX / subtractX / interval / dateDiff
+enum TUnit { U_SECOND, U_MINUTE, U_HOUR, U_DAY, U_WEEK, U_MONTH, U_QUARTER, U_YEAR };
 struct Lowering {
   std::string err;
   bool fail(const std::string &m) {
@@ -57,7 +64,8 @@ struct PNode {
   int op = NUT_P_I64;
   int col = -1;  // NUT_P_COL: plan column
   CVal c;        // NUT_P_I64 / NUT_P_F64 constant
-  int arg = 0;   // NUT_P_DATEPART: nut_date_part; P_SUBSTR: the 1-based byte offset
+  int arg = 0;   // NUT_P_DATEPART / TIMEPART / DATETRUNC: the part; P_SUBSTR: the 1-based byte offset;
+                 // P_ADDIV: TUnit (| kFromInterval)
 };
 using PProg = std::vector<PNode>;
 
@@ -215,6 +223,17 @@ namespace plan {
 // `substring(col, arg, c.v)` over one (c.v = kHuge: to the end), lowered at execution to
 // COL + MAP from the column's codes to its substrings' codes in the same dictionary
 constexpr int P_LIKE = 1000, P_ILIKE = 1001, P_SUBSTR = 1002;
+// Kind-dependent calendar nodes.  Column kinds are known only at execution,
+// so build_spec resolves these against the kind of their operand:
+//   P_DAYS   x -> the day number a day function reads: TIMEPART(DATE) of a Datetime, else x
+//   P_SECS   x -> x, the seconds a time function reads: a Date operand is a plan error
+//            (c.s = the function call's text, for the message)
+//   P_TODATE toDate(x): x itself if it is a Date, else TIMEPART(DATE)
+//   P_ADDIV  x, n -> x plus n units (arg = TUnit): seconds for a Datetime, days / ADDMONTHS
+//            for a Date or plain operand; kFromInterval in arg: from `x + interval n unit`,
+//            where a unit below a day needs a Datetime (addSeconds(x, n) reads seconds)
+constexpr int P_DAYS = 1003, P_SECS = 1004, P_TODATE = 1005, P_ADDIV = 1006;
+constexpr int kFromInterval = 0x100;
 // a node that reads its plan column (col)
 inline bool reads_col(int op) { return op == NUT_P_COL || op == P_LIKE || op == P_ILIKE || op == P_SUBSTR; }
 // ------------------------------------------------------------------ predicate resolution
@@ -273,10 +292,21 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
 // read narrow bytes; every other consumer gets 8-byte words.
 // the type a column computes as and results report: int64 / float64 (strings stay)
 inline int logical_type(int t) { return t == NUT_T_STR ? t : type_is_float(t) ? NUT_T_F64 : NUT_T_I64; }
-inline bool col_narrow(const nut_column *c) { return type_known(c->type) && type_width(c->type) < 8; }
+// nut_column.type without the temporal-kind flags (NUT_COL_AS_DATE / AS_DATETIME: int64
+// columns only, one at most — otherwise -1, which no consumer knows); every read of a bound
+// column's type goes through here
+constexpr int kColKindMask = NUT_COL_AS_DATE | NUT_COL_AS_DATETIME;
+inline int col_type(const nut_column *c) {
+  const int k = c->type & kColKindMask, t = c->type & ~kColKindMask;
+  return k && ((t & ~NUT_COL_HOST) != NUT_T_I64 || k == kColKindMask) ? -1 : t;
+}
+inline int col_kind(const nut_column *c) {
+  return (c->type & NUT_COL_AS_DATETIME) ? K_DATETIME : (c->type & NUT_COL_AS_DATE) ? K_DATE : K_PLAIN;
+}
+inline bool col_narrow(const nut_column *c) { return type_known(col_type(c)) && type_width(col_type(c)) < 8; }
 // out[i] = the 8-byte word of col[idx[i]]: carries a bound column of any type through row ids
 inline nut_status gather_col(nut_ctx *c, const nut_column *col, const int64_t *idx, uint64_t n, uint64_t *out) {
-  return nut_gather_typed(c, col->data, col->type, idx, n, 0, out);
+  return nut_gather_typed(c, col->data, col_type(col), idx, n, 0, out);
 }
 // cols with every narrow column replaced by a widened temporary (nut_gather_typed, idx =
 // NULL; freed with `bufs`): for consumers that need whole 8-byte columns (joins).  *out =
@@ -309,6 +339,10 @@ int date_fn(sv n);
 unsigned month_days(int64_t y, unsigned m);
 bool parse_date(sv s, int64_t &days);
 int64_t add_months(int64_t days, i128 months);
+// host twins of the TIMEPART / DATETRUNC / ADDMONTHS program ops (constants fold with these)
+int64_t time_part(int64_t s, int part);
+int64_t date_trunc(int64_t d, int unit);
+int64_t add_months_op(int64_t d, int64_t n);
 bool const_eval(const Expr &e, CVal &out, Lowering &L);
 std::string cval_str(const CVal &c);
 i128 dec_floor(const Decimal &d, bool &frac);

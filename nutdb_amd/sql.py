@@ -29,7 +29,9 @@ from ._lib import (NUT_COL_HOST, NUT_OK, STMT_KINDS, TOKEN_TYPES, NutColumn, Nut
 
 # column type names of Plan.route / Plan.prepare -> nut_type
 TYPE_NAMES = {"int64": T_I64, "float64": T_F64, "int32": _L.T_I32, "int16": _L.T_I16, "int8": _L.T_I8,
-              "uint32": _L.T_U32, "uint16": _L.T_U16, "uint8": _L.T_U8, "float32": _L.T_F32}
+              "uint32": _L.T_U32, "uint16": _L.T_U16, "uint8": _L.T_U8, "float32": _L.T_F32,
+              # int64 columns with a temporal kind: day numbers / seconds since 1970-01-01
+              "date": T_I64 | _L.NUT_COL_AS_DATE, "datetime": T_I64 | _L.NUT_COL_AS_DATETIME}
 
 NUT_ERR_PARSE = 6
 NUT_ERR_CAPACITY = 5
@@ -194,7 +196,8 @@ class Plan:
     def prepare(self, types: Dict[str, str]) -> None:
         """Compile an expression-mode plan's kernel ahead of execute (hipRTC, no GPU
         needed); `types` = {column: "int64" | "float64" | "int32" | "int16" | "int8" | "uint32" |
-        "uint16" | "uint8" | "float32"}.  No-op for fused plans."""
+        "uint16" | "uint8" | "float32" | "date" | "datetime"} (the last two: int64 day numbers /
+        seconds, which the calendar functions tell apart).  No-op for fused plans."""
         arr = (NutColumn * max(len(types), 1))()
         names = [k.encode() for k in types]
         for i, (name, t) in enumerate(types.items()):
@@ -218,10 +221,17 @@ class Plan:
         return _text(fn, self._h)
 
     def execute(self, ex, columns: Dict[str, "object"], nrows: Optional[int] = None,
-                group_hint: int = 0) -> Dict[str, np.ndarray]:
+                group_hint: int = 0, types: Optional[Dict[str, str]] = None) -> Dict[str, np.ndarray]:
         """Run on the GPU of executor `ex` with `columns` = {name: 1-D int64/float64 CUDA
-        tensor}.  Returns {output name: numpy array} in SELECT-list order."""
+        tensor}.  Returns {output name: numpy array} in SELECT-list order.  `types` =
+        {column: "date" | "datetime"} declares int64 columns as day numbers / seconds."""
         arr, keep, n = self._bind(columns)
+        for i, name in enumerate(columns):
+            kind = (types or {}).get(name)
+            if kind is not None:
+                if kind not in ("date", "datetime") or (arr[i].type & 0xFF) != T_I64:
+                    raise ValueError(f"column {name!r}: types= takes 'date' or 'datetime' for int64 columns")
+                arr[i].type |= TYPE_NAMES[kind] & ~0xFF
         rows = nrows if nrows is not None else (n or 0)
         res = C.c_void_p()
         ex._bind_stream()

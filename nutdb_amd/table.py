@@ -87,6 +87,10 @@ class Table:
             else:
                 if kind == "date" and len(values) and isinstance(values[0], str):
                     values = (np.array(values, dtype="datetime64[D]") - np.datetime64("1970-01-01", "D")).astype(np.int64)
+                if kind == "datetime" and len(values) and (
+                        isinstance(values[0], str) or np.asarray(values).dtype.kind == "M"):
+                    # ISO strings / numpy.datetime64 of any unit: whole seconds since 1970-01-01 (floor)
+                    values = np.asarray(values, dtype="datetime64[s]").astype(np.int64)
                 a = np.ascontiguousarray(values, dtype=_NP[(kind, width)])
                 check(lib.nut_table_append(self.ex.ctx, self._h, j, a.ctypes.data_as(C.c_void_p), None, len(a)),
                       "nut_table_append")
