@@ -15,6 +15,7 @@
 //   * the kernel headers are embedded at build time (_gen/jit_headers.inc, written by
 //     nutdb_amd/build.py), so the library needs no source tree at run time.
 #include "jit.hpp"
+#include "prog_ops.hpp"
 
 #include <hip/hiprtc.h>
 #include <string.h>
@@ -74,10 +75,7 @@ struct Gen {
       const nut_prog_node &nd = p->node[i];
       PVal a[3];
       const int op = nd.op;
-      const int arity = op <= NUT_P_F64 ? 0 : (op == NUT_P_NOT || op == NUT_P_BITNOT || op == NUT_P_ABS ||
-                                                op == NUT_P_TO_F64 || op == NUT_P_LOOKUP || op == NUT_P_DATEPART || op == NUT_P_MAP ||
-                                                op == NUT_P_TIMEPART || op == NUT_P_DATETRUNC) ? 1
-                                                                                         : op == NUT_P_IF ? 3 : 2;
+      const int arity = prog_arity(op);
       if (op < 0 || op > NUT_P_ADDMONTHS) return fail("unknown program op " + std::to_string(op));
       if (!pop(arity, a)) return fail("program stack underflow at node " + std::to_string(i));
       PVal r;
@@ -216,23 +214,8 @@ typedef unsigned short uint16_t;
 typedef unsigned char uint8_t;
 #include "agg_kernel.hpp"
 #include "select_kernel.hpp"
+#include "prog_ops.hpp"  // the integer and calendar helpers (jdiv ... jaddmonths)
 namespace nut {
-// integer helpers of the expression semantics (include/nutexec.h, nut_prog_op)
-__device__ __forceinline__ int64_t jmod(int64_t a, int64_t b, bool &err) {
-  if (b == 0) { err = true; return 0; }
-  return b == -1 ? 0 : a % b;
-}
-__device__ __forceinline__ int64_t jdiv(int64_t a, int64_t b, bool &err) {
-  if (b == 0) { err = true; return 0; }
-  return b == -1 ? (int64_t)(0 - (uint64_t)a) : a / b;
-}
-__device__ __forceinline__ int64_t jshl(int64_t a, int64_t b) {
-  return (b >= 0 && b < 64) ? (int64_t)((uint64_t)a << b) : 0;
-}
-__device__ __forceinline__ int64_t jshr(int64_t a, int64_t b) {
-  return (b >= 0 && b < 64) ? (a >> b) : (a < 0 ? -1 : 0);
-}
-__device__ __forceinline__ int64_t jabs(int64_t a) { return a < 0 ? (int64_t)(0 - (uint64_t)a) : a; }
 // f64 MOD: C fmod with the NaN rule of f64 DIV on this device (include/nutexec.h): a NaN
 // operand passes through quieted, the first operand's first; an invalid operation (x mod 0,
 // inf mod y) gives the negative quiet NaN, as 0 / 0 does.  The device library's fmod returns
@@ -253,107 +236,6 @@ __device__ __forceinline__ bool jlookup(int64_t x, uint64_t t, uint64_t n) {
 __device__ __forceinline__ int64_t jmap(int64_t x, uint64_t t, uint64_t n) {
   if ((uint64_t)x >= n) return -1;
   return ((const int64_t *)t)[x];
-}
-// ---- calendar (proleptic Gregorian; day 0 = 1970-01-01).  Every divisor is a literal: the
-// compiler turns each division into multiplies and shifts (the device has no 64-bit divide).
-__device__ __forceinline__ int64_t jclamp(int64_t x, const int64_t m) { return x < -m ? -m : x > m ? m : x; }
-// floor division by a positive literal g, and the remainder in [0, g)
-__device__ __forceinline__ int64_t jfdiv(int64_t a, const int64_t g) {
-  const int64_t q = a / g;
-  return a - q * g < 0 ? q - 1 : q;
-}
-__device__ __forceinline__ int64_t jfrem(int64_t a, const int64_t g) { return a - jfdiv(a, g) * g; }
-// a civil date: year = y400 + yr (y400 a multiple of 400, yr in [0, 400]), month 1-12, day
-// of month 1-31; doy / mp = day and month of the year that starts on March 1
-struct JDate {
-  int64_t y400;
-  uint32_t yr, m, d, doy, mp;
-};
-__device__ __forceinline__ bool jleap(uint32_t yr) { return (yr % 4 == 0 && yr % 100 != 0) || yr % 400 == 0; }
-__device__ __forceinline__ uint32_t jmonth_days(uint32_t yr, uint32_t m) {
-  return m == 2 ? (jleap(yr) ? 29u : 28u) : 30u + ((m + (m >> 3)) & 1u);
-}
-// civil-from-days of a clamped day number: one 64-bit division, the rest in 32 bits
-__device__ __forceinline__ JDate jcivil(int64_t d) {
-  const int64_t z = d + 719468;
-  const int64_t era = jfdiv(z, 146097);
-  const uint32_t doe = (uint32_t)(z - era * 146097);
-  const uint32_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
-  JDate c;
-  c.doy = doe - (365 * yoe + yoe / 4 - yoe / 100);
-  c.mp = (5 * c.doy + 2) / 153;
-  c.d = c.doy - (153 * c.mp + 2) / 5 + 1;
-  c.m = c.mp < 10 ? c.mp + 3 : c.mp - 9;
-  c.y400 = era * 400;
-  c.yr = yoe + (c.m <= 2 ? 1u : 0u);
-  return c;
-}
-// days-from-civil of year y400 + yr (yr in [0, 400)), month m, day d
-__device__ __forceinline__ int64_t jdays(int64_t y400, uint32_t yr, uint32_t m, uint32_t d) {
-  if (m <= 2) {  // January and February belong to the March-based year before
-    if (yr == 0) y400 -= 400, yr = 399;
-    else yr -= 1;
-  }
-  const uint32_t doy = (153 * (m > 2 ? m - 3 : m + 9) + 2) / 5 + d - 1;
-  const uint32_t doe = yr * 365 + yr / 4 - yr / 100 + doy;
-  return (y400 / 400) * 146097 + (int64_t)doe - 719468;
-}
-// P = nut_date_part.  d is clamped to +-2^40 days first, so no intermediate overflows.
-__device__ __forceinline__ int64_t jdatepart(int64_t d, const int P) {
-  d = jclamp(d, 1ll << 40);
-  if (P == 4) return jfrem(d + 3, 7) + 1;  // 1970-01-01 was a Thursday (4)
-  if (P == 10) return jfdiv(d + 3, 7);
-  const JDate c = jcivil(d);
-  const int64_t y = c.y400 + (int64_t)c.yr, m = c.m;
-  if (P == 0) return y;
-  if (P == 1) return m;
-  if (P == 2) return c.d;
-  if (P == 6) return y * 100 + m;
-  if (P == 7) return y * 10000 + m * 100 + c.d;
-  if (P == 3) return (m - 1) / 3 + 1;
-  if (P == 8) return y * 12 + m;
-  if (P == 9) return y * 4 + (m - 1) / 3;
-  // day of year: January / February are days 306.. of the March-based year
-  return c.doy >= 306 ? (int64_t)c.doy - 305 : (int64_t)c.doy + 60 + (jleap(c.yr) ? 1 : 0);
-}
-// P = nut_time_part; s (seconds) is clamped to +-2^40 days first
-__device__ __forceinline__ int64_t jtimepart(int64_t s, const int P) {
-  s = jclamp(s, (1ll << 40) * 86400);
-  if (P == 0) return jfdiv(s, 86400);
-  if (P == 1) return jfrem(s, 86400) / 3600;
-  if (P == 2) return jfrem(s, 3600) / 60;
-  if (P == 3) return jfrem(s, 60);
-  if (P == 4) return s - jfrem(s, 60);
-  if (P == 5) return s - jfrem(s, 300);
-  if (P == 6) return s - jfrem(s, 900);
-  if (P == 7) return s - jfrem(s, 3600);
-  return s - jfrem(s, 86400);
-}
-// P = nut_date_trunc; a day number
-__device__ __forceinline__ int64_t jdatetrunc(int64_t d, const int P) {
-  d = jclamp(d, 1ll << 40);
-  if (P == 0) return d - jfrem(d + 3, 7);
-  if (P == 1) return d - jfrem(d + 4, 7);
-  const JDate c = jcivil(d);
-  if (P == 2) return d - (int64_t)c.d + 1;
-  if (P == 5) return d - (int64_t)c.d + (int64_t)jmonth_days(c.yr, c.m);
-  const int64_t jan1 = c.doy >= 306 ? d - ((int64_t)c.doy - 306) : d - ((int64_t)c.doy + 59 + (jleap(c.yr) ? 1 : 0));
-  if (P == 4) return jan1;
-  // quarter: April, July and October start on days 31, 122 and 214 of the March-based year
-  if (c.m <= 3) return jan1;
-  const uint32_t q0 = c.m <= 6 ? 31u : c.m <= 9 ? 122u : 214u;
-  return d - (int64_t)c.doy + (int64_t)q0;
-}
-// n months from day d, the day of month clamped to the target month's length
-__device__ __forceinline__ int64_t jaddmonths(int64_t d, int64_t n) {
-  d = jclamp(d, 1ll << 40);
-  n = jclamp(n, 1ll << 36);
-  const JDate c = jcivil(d);
-  const int64_t t = (c.y400 + (int64_t)c.yr) * 12 + ((int64_t)c.m - 1) + n;
-  const int64_t e = jfdiv(t, 4800);  // 400 years of months
-  const uint32_t r = (uint32_t)(t - e * 4800), yr = r / 12, m = r - yr * 12 + 1;
-  const uint32_t md = jmonth_days(yr, m);
-  return jdays(e * 400, yr, m, c.d < md ? c.d : md);
 }
 )";
 

@@ -273,7 +273,8 @@ nut_status groupby_packed(nut_ctx *c, const nut_plan &p, const nut_agg_spec &s, 
   return NUT_OK;
 }
 
-// evaluation of an OUT_EXPR output for group i (nut_prog arithmetic semantics)
+// evaluation of an OUT_EXPR output for group i (nut_prog arithmetic semantics: the integer
+// arms are prog_ops.hpp's; f64 % is the host's fmod)
 struct XVal {
   bool is_int;
   int64_t i;
@@ -291,7 +292,7 @@ XVal xpr_eval(const XNode &x, const std::vector<std::vector<uint64_t>> &cols, co
     return XVal{false, 0, f};
   }
   const XVal a = xpr_eval(x.kids[0], cols, types, g, div0);
-  if (x.k == X_ABS) return a.is_int ? XVal{true, a.i < 0 ? (int64_t)(0 - (uint64_t)a.i) : a.i, 0.0} : XVal{false, 0, fabs(a.f)};
+  if (x.k == X_ABS) return a.is_int ? XVal{true, jabs(a.i), 0.0} : XVal{false, 0, fabs(a.f)};
   if (x.k == X_TOF) return XVal{false, 0, a.as_f()};
   const XVal b = xpr_eval(x.kids[1], cols, types, g, div0);
   const bool ii = a.is_int && b.is_int;
@@ -309,12 +310,7 @@ XVal xpr_eval(const XNode &x, const std::vector<std::vector<uint64_t>> &cols, co
         }
         return XVal{false, 0, fmod(a.as_f(), b.as_f())};
       }
-      if (b.i == 0) {
-        div0 = true;
-        return XVal{true, 0, 0.0};
-      }
-      if (b.i == -1) return XVal{true, x.k == X_MOD ? 0 : (int64_t)(0 - (uint64_t)a.i), 0.0};
-      return XVal{true, x.k == X_MOD ? a.i % b.i : a.i / b.i, 0.0};
+      return XVal{true, x.k == X_MOD ? jmod(a.i, b.i, div0) : jdiv(a.i, b.i, div0), 0.0};
     default: return XVal{true, 0, 0.0};
   }
 }

@@ -12,7 +12,7 @@
 //     converted with correct rounding for f64 columns), toDate('YYYY-MM-DD') and
 //     date +/- interval n day|month|year, as days since 1970-01-01;
 //     toDateTime('YYYY-MM-DD hh:mm:ss') as seconds; every calendar function of constants
-//     (const_eval, with the host twins of the device functions: DESIGN.md §3.12).
+//     (const_eval, with the program ops' own functions, prog_ops.hpp: DESIGN.md §3.12).
 //   * SELECT-list FnCall Others(name): sum/count/min/max/avg, case-insensitive
 //     (the parser keeps the original case, mod.rs:1305); count(*) is the wildcard
 //     Identifier (mod.rs:1271); avg = sum / count.  Arguments: a column or one of the
@@ -80,6 +80,9 @@ i128 sat_from_u128(u128 m, bool neg) {
   return neg ? -v : v;
 }
 
+// Literal dates: 'YYYY-MM-DD' parsing and `date +/- interval n month` over constants, for any
+// int64 year and an unclamped 128-bit month count.  (Not the program ops: DATEPART, DATETRUNC
+// and ADDMONTHS clamp their operands and are defined once, in prog_ops.hpp.)
 // days since 1970-01-01 of a proleptic Gregorian date (civil-from-days inverse)
 int64_t days_from_civil(int64_t y, unsigned m, unsigned d) {
   y -= m <= 2;
@@ -102,31 +105,7 @@ void civil_from_days(int64_t z, int64_t &y, unsigned &m, unsigned &d) {
   y += m <= 2;
 }
 bool leap(int64_t y) { return (y % 4 == 0 && y % 100 != 0) || y % 400 == 0; }
-// floor division / modulo by a positive g, and the operand clamps of the calendar ops
-int64_t floor_div(int64_t a, int64_t g) { return a / g - (a % g < 0 ? 1 : 0); }
-int64_t floor_mod(int64_t a, int64_t g) { return a - floor_div(a, g) * g; }
-int64_t clamp64(int64_t x, int64_t m) { return std::max(-m, std::min(m, x)); }
 int64_t sat64(i128 v) { return v > INT64_MAX ? INT64_MAX : v < INT64_MIN ? INT64_MIN : (int64_t)v; }
-// nut_date_part of a day number (the DATEPART program op's host twin, for constants)
-int64_t date_part(int64_t d, int part) {
-  d = std::max<int64_t>(-(1ll << 40), std::min<int64_t>(1ll << 40, d));
-  int64_t y;
-  unsigned m, dd;
-  civil_from_days(d, y, m, dd);
-  switch (part) {
-    case NUT_DP_YEAR: return y;
-    case NUT_DP_MONTH: return m;
-    case NUT_DP_DAY: return dd;
-    case NUT_DP_QUARTER: return (m - 1) / 3 + 1;
-    case NUT_DP_WEEKDAY: return ((d % 7 + 7) % 7 + 3) % 7 + 1;
-    case NUT_DP_YYYYMM: return y * 100 + m;
-    case NUT_DP_YYYYMMDD: return y * 10000 + m * 100 + dd;
-    case NUT_DP_REL_MONTH: return y * 12 + m;
-    case NUT_DP_REL_QUARTER: return y * 4 + (m - 1) / 3;
-    case NUT_DP_REL_WEEK: return floor_div(d + 3, 7);
-    default: return d - days_from_civil(y, 1, 1) + 1;
-  }
-}
 // SQL date functions (ClickHouse names; getX spellings as in the reference's fixtures):
 // the nut_date_part they compute, or -1
 int date_fn(sv n) {
@@ -163,7 +142,7 @@ bool parse_date(sv s, int64_t &days) {
   return true;
 }
 
-// date +/- n months, clamping the day to the target month's length
+// constant date +/- interval n months (any n), the day clamped to the target month's length
 int64_t add_months(int64_t days, i128 months) {
   int64_t y;
   unsigned m, d;
@@ -174,35 +153,6 @@ int64_t add_months(int64_t days, i128 months) {
   unsigned nd = std::min(d, month_days(ny, nm));
   return days_from_civil(ny, nm, nd);
 }
-
-// host twins of the TIMEPART / DATETRUNC / ADDMONTHS program ops (jit.cpp: jtimepart,
-// jdatetrunc, jaddmonths), clamps included
-int64_t time_part(int64_t s, int part) {
-  s = clamp64(s, (1ll << 40) * 86400);
-  static const int64_t g[] = {60, 300, 900, 3600, 86400};
-  switch (part) {
-    case NUT_TP_DATE: return floor_div(s, 86400);
-    case NUT_TP_HOUR: return floor_mod(s, 86400) / 3600;
-    case NUT_TP_MINUTE: return floor_mod(s, 3600) / 60;
-    case NUT_TP_SECOND: return floor_mod(s, 60);
-    default: return s - floor_mod(s, g[part - NUT_TP_START_MINUTE]);
-  }
-}
-int64_t date_trunc(int64_t d, int unit) {
-  d = clamp64(d, 1ll << 40);
-  if (unit == NUT_DT_WEEK_MONDAY) return d - floor_mod(d + 3, 7);
-  if (unit == NUT_DT_WEEK_SUNDAY) return d - floor_mod(d + 4, 7);
-  int64_t y;
-  unsigned m, dd;
-  civil_from_days(d, y, m, dd);
-  switch (unit) {
-    case NUT_DT_MONTH: return days_from_civil(y, m, 1);
-    case NUT_DT_QUARTER: return days_from_civil(y, (m - 1) / 3 * 3 + 1, 1);
-    case NUT_DT_YEAR: return days_from_civil(y, 1, 1);
-    default: return days_from_civil(y, m, month_days(y, m));
-  }
-}
-int64_t add_months_op(int64_t d, int64_t n) { return add_months(clamp64(d, 1ll << 40), clamp64(n, 1ll << 36)); }
 
 namespace {
 int64_t wadd(int64_t a, int64_t b) { return (int64_t)((uint64_t)a + (uint64_t)b); }
@@ -288,10 +238,10 @@ bool add_units(int64_t x, int kind, int unit, int64_t n, bool from_interval, int
   } else {
     const int64_t mo = wmul(n, unit == U_MONTH ? 1 : unit == U_QUARTER ? 3 : 12);
     if (kind == K_DATETIME) {
-      out = wadd(wmul(add_months_op(time_part(x, NUT_TP_DATE), mo), 86400), wsub(x, time_part(x, NUT_TP_START_DAY)));
+      out = wadd(wmul(jaddmonths(jtimepart(x, NUT_TP_DATE), mo), 86400), wsub(x, jtimepart(x, NUT_TP_START_DAY)));
       okind = K_DATETIME;
     } else {
-      out = add_months_op(x, mo);
+      out = jaddmonths(x, mo);
       okind = K_DATE;
     }
   }
@@ -301,11 +251,11 @@ bool add_units(int64_t x, int kind, int unit, int64_t n, bool from_interval, int
 bool diff_count(int64_t x, int kind, int unit, int64_t &out) {
   if (unit <= U_HOUR) {
     if (kind == K_DATE) return false;
-    out = unit == U_SECOND ? x : floor_div(clamp64(x, (1ll << 40) * 86400), unit == U_MINUTE ? 60 : 3600);
+    out = unit == U_SECOND ? x : jfdiv(jclamp(x, (1ll << 40) * 86400), unit == U_MINUTE ? 60 : 3600);
     return true;
   }
-  const int64_t d = kind == K_DATETIME ? time_part(x, NUT_TP_DATE) : x;
-  out = unit == U_DAY ? d : date_part(d, unit == U_WEEK ? NUT_DP_REL_WEEK : unit == U_MONTH ? NUT_DP_REL_MONTH
+  const int64_t d = kind == K_DATETIME ? jtimepart(x, NUT_TP_DATE) : x;
+  out = unit == U_DAY ? d : jdatepart(d, unit == U_WEEK ? NUT_DP_REL_WEEK : unit == U_MONTH ? NUT_DP_REL_MONTH
                                          : unit == U_QUARTER ? NUT_DP_REL_QUARTER : NUT_DP_YEAR);
   return true;
 }
@@ -377,9 +327,9 @@ bool const_eval(const Expr &e, CVal &out, Lowering &L) {
     if (!const_eval(e.kids[0], x, L) || !x.is_int || x.is_str) return false;
     out.is_int = true;
     // (a Datetime constant: its day first)
-    const int64_t d = x.kind == K_DATETIME ? time_part(sat64(x.v), NUT_TP_DATE)
+    const int64_t d = x.kind == K_DATETIME ? jtimepart(sat64(x.v), NUT_TP_DATE)
                                            : (int64_t)std::max<i128>(-(i128(1) << 41), std::min<i128>(i128(1) << 41, x.v));
-    out.v = date_part(d, date_fn(e.id.name));
+    out.v = jdatepart(d, date_fn(e.id.name));
     return true;
   }
   if (e.k == EK::FnCall && e.fn() == FnKind::Others) {  // the other calendar functions of constants
@@ -390,7 +340,7 @@ bool const_eval(const Expr &e, CVal &out, Lowering &L) {
     if (ieq(n, "todate") && na == 1) {
       if (!const_int(e.kids[0], x, L)) return false;
       out = CVal{};
-      out.v = x.kind == K_DATE ? x.v : (i128)time_part(sat64(x.v), NUT_TP_DATE);
+      out.v = x.kind == K_DATE ? x.v : (i128)jtimepart(sat64(x.v), NUT_TP_DATE);
       out.kind = K_DATE;
       return true;
     }
@@ -398,7 +348,7 @@ bool const_eval(const Expr &e, CVal &out, Lowering &L) {
       if (!const_int(e.kids[0], x, L)) return false;
       if (x.kind == K_DATE) return L.fail("'" + expr_text(e) + "': a time function over a Date (it reads seconds)");
       out = CVal{};
-      out.v = time_part(sat64(x.v), cf.arg);
+      out.v = jtimepart(sat64(x.v), cf.arg);
       out.kind = cf.arg >= NUT_TP_START_MINUTE && x.kind == K_DATETIME ? K_DATETIME : K_PLAIN;
       return true;
     }
@@ -410,7 +360,7 @@ bool const_eval(const Expr &e, CVal &out, Lowering &L) {
         unit = y.v == 1 ? NUT_DT_WEEK_MONDAY : NUT_DT_WEEK_SUNDAY;
       }
       out = CVal{};
-      out.v = date_trunc(x.kind == K_DATETIME ? time_part(sat64(x.v), NUT_TP_DATE) : sat64(x.v), unit);
+      out.v = jdatetrunc(x.kind == K_DATETIME ? jtimepart(sat64(x.v), NUT_TP_DATE) : sat64(x.v), unit);
       out.kind = K_DATE;
       return true;
     }
@@ -517,9 +467,7 @@ int mirror(int op) { return op == NUT_LT ? NUT_GT : op == NUT_GT ? NUT_LT : op =
 int pnode_arity(int op) {
   if (op == P_LIKE || op == P_ILIKE || op == P_SUBSTR) return 0;
   if (op == P_DAYS || op == P_SECS || op == P_TODATE) return 1;
-  return op <= NUT_P_F64 ? 0 : (op == NUT_P_NOT || op == NUT_P_BITNOT || op == NUT_P_ABS || op == NUT_P_TO_F64 ||
-                                op == NUT_P_DATEPART || op == NUT_P_TIMEPART || op == NUT_P_DATETRUNC) ? 1
-                               : op == NUT_P_IF ? 3 : 2;
+  return prog_arity(op);
 }
 
 // bytes of the UTF-8 sequence starting at s[i] (a stray continuation byte counts alone)

@@ -15,6 +15,7 @@
 #include <tuple>
 
 #include "common.hpp"
+#include "prog_ops.hpp"
 #include "sort.hpp"
 #include "sql_ast.hpp"
 #include "sql_lexer.hpp"
@@ -331,18 +332,15 @@ bool ieq(sv a, sv b);
 std::string i128_str(i128 v);
 void json_str(std::string &o, sv s);
 i128 sat_from_u128(u128 m, bool neg);
+// literal dates and `date +/- interval n month` over constants (any year, any month count);
+// the program ops fold with their own functions (prog_ops.hpp)
 int64_t days_from_civil(int64_t y, unsigned m, unsigned d);
 void civil_from_days(int64_t z, int64_t &y, unsigned &m, unsigned &d);
 bool leap(int64_t y);
-int64_t date_part(int64_t d, int part);
-int date_fn(sv n);
 unsigned month_days(int64_t y, unsigned m);
 bool parse_date(sv s, int64_t &days);
 int64_t add_months(int64_t days, i128 months);
-// host twins of the TIMEPART / DATETRUNC / ADDMONTHS program ops (constants fold with these)
-int64_t time_part(int64_t s, int part);
-int64_t date_trunc(int64_t d, int unit);
-int64_t add_months_op(int64_t d, int64_t n);
+int date_fn(sv n);
 bool const_eval(const Expr &e, CVal &out, Lowering &L);
 std::string cval_str(const CVal &c);
 i128 dec_floor(const Decimal &d, bool &frac);

@@ -1,5 +1,5 @@
-"""Edge operands of the expression semantics (include/nutexec.h nut_prog; csrc/jit.cpp
-prelude: jmod, jdiv, jshl, jshr, jabs, jfmod, jdatepart, the int -> f64 conversions, the
+"""Edge operands of the expression semantics (include/nutexec.h nut_prog; csrc/prog_ops.hpp:
+jmod, jdiv, jshl, jshr, jabs, jdatepart; the jit.cpp prelude's jfmod; the int -> f64 conversions, the
 constants passed as kernel arguments), and the programs that read them.
 
 tests/test_expr_edges_cpu.py pins the numpy oracle (oracle/expr.py) on these operands against
@@ -208,7 +208,7 @@ KEY_AGGS = [("count", None, None), ("sum", C1, None), ("min", C0, None), ("max",
 
 # ------------------------------------------------------------------ SQL
 DATE_FNS = ["toYear", "toMonth", "toDayOfMonth", "toQuarter", "toDayOfWeek", "toDayOfYear", "toYYYYMM", "toYYYYMMDD"]
-FOLD_DAYS = [-719469, -719468, 11016, 2**40 + 1]  # toYYYYMMDD(<literal>) folds on the host (sql_lower.cpp date_part)
+FOLD_DAYS = [-719469, -719468, 11016, 2**40 + 1]  # toYYYYMMDD(<literal>) folds on the host (const_eval calls prog_ops.hpp jdatepart)
 A, FC, D = [("col", 0)], [("col", 1)], [("col", 2)]  # columns a (int64), f (float64), d (int64 days)
 # (output name, SQL item, the program it lowers to)
 SQL_ITEMS = [

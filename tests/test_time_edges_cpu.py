@@ -1,7 +1,7 @@
 """CPU: the exact restatement of the calendar ops (tests/time_edges.py) against `datetime`, the
 known answers, nut_prog_type over the new ops, every kernel tests/test_gpu_time.py runs
-compiled here with hipRTC (no GPU needed), constant folding on the host (the twins of the
-device functions), the temporal kinds at binding, and every new SQL name."""
+compiled here with hipRTC (no GPU needed), constant folding on the host (the same functions,
+csrc/prog_ops.hpp), the temporal kinds at binding, and every new SQL name."""
 import calendar
 import ctypes as C
 import datetime

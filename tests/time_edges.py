@@ -1,5 +1,5 @@
 """Edge operands of the calendar program ops (include/nutexec.h: TIMEPART, DATETRUNC,
-ADDMONTHS and the REL_* parts of DATEPART; csrc/jit.cpp prelude: jtimepart, jdatetrunc,
+ADDMONTHS and the REL_* parts of DATEPART; csrc/prog_ops.hpp: jtimepart, jdatetrunc,
 jaddmonths, jdatepart), and an exact restatement of each in Python integers.
 
 oracle/expr.py does not know these ops, so the restatement below is the reference:
