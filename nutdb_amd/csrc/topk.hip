@@ -87,10 +87,9 @@ extern "C" nut_status nut_topk_positions(nut_ctx *c, const void *keys, int key_t
   if (k >= n) {  // every key
     *count_host = n;
     if (n > cap) return NUT_ERR_CAPACITY;
-    if (!positions) {
-    c->timer.end(st);
-    return fail(NUT_ERR_INVALID_ARG, "nut_topk_positions: NULL output");
-  }
+    // (no timer.end here: nothing was begun, and it would record the end event of the
+    // context's previous timed kernel again, stretching that kernel's time up to now)
+    if (!positions) return fail(NUT_ERR_INVALID_ARG, "nut_topk_positions: NULL output");
     hipLaunchKernelGGL(topk_iota_kernel, dim3((unsigned)std::min<uint64_t>((n + 255) / 256, 4096)), dim3(256), 0, st,
                        positions, n);
     NUT_HIP(hipGetLastError());

@@ -1,8 +1,10 @@
 """Shared test helpers: the golden script's numpy restatement + comparison utilities."""
+import ctypes as C
 import importlib.util
 from pathlib import Path
 
 import numpy as np
+import torch
 
 _spec = importlib.util.spec_from_file_location("make_golden", Path(__file__).parent / "golden" / "make_golden.py")
 mg = importlib.util.module_from_spec(_spec)
@@ -141,3 +143,47 @@ def nf_covers_all(sum_words, what=""):
     assert (s == np.inf).any() and (s == -np.inf).any(), what
     assert ((s != 0) & (np.abs(s) < F64_MIN_NORMAL)).any(), what
     assert (s == 0).any(), what
+
+
+# ----------------------------------------------------------------------------- sort helpers
+# (shared by test_gpu_order_by.py and test_gpu_sort_paths.py)
+def dev(x, ex):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(ex.device)
+
+
+def ukey(v, desc=False):
+    """The sort's unsigned order key: int64 sign-flipped, float64 by the IEEE total order."""
+    b = np.ascontiguousarray(v).view(np.uint64)
+    if v.dtype == np.float64:
+        u = np.where(b >> np.uint64(63), ~b, b | np.uint64(1 << 63))
+    else:
+        u = b ^ np.uint64(1 << 63)
+    return ~u if desc else u
+
+
+def sort_pairs(ex, keys, desc=False, vals=None):
+    from nutdb_amd._lib import T_F64, T_I64, check, lib
+    n = len(keys)
+    k = dev(keys, ex)
+    v = dev(vals, ex) if vals is not None else None
+    out = torch.empty(max(n, 1), dtype=torch.int64, device=ex.device)
+    ex._bind_stream()
+    check(lib.nut_sort_pairs(ex.ctx, C.c_void_p(k.data_ptr() if n else None), T_F64 if keys.dtype == np.float64 else T_I64,
+                             int(desc), C.c_void_p(v.data_ptr()) if v is not None else None,
+                             C.c_void_p(out.data_ptr()), n), "nut_sort_pairs")
+    ex.sync()
+    return out[:n].cpu().numpy()
+
+
+def topk_positions(ex, keys, k, desc=False, cap=None):
+    from nutdb_amd._lib import T_F64, T_I64, lib
+    n = len(keys)
+    d = dev(keys, ex)
+    cap = n if cap is None else cap
+    out = torch.empty(max(cap, 1), dtype=torch.int64, device=ex.device)
+    cnt = C.c_uint64()
+    ex._bind_stream()
+    st = lib.nut_topk_positions(ex.ctx, C.c_void_p(d.data_ptr()), T_F64 if keys.dtype == np.float64 else T_I64,
+                                1 if desc else 0, n, k, C.c_void_p(out.data_ptr()), cap, C.byref(cnt))
+    ex.sync()
+    return st, cnt.value, out[: cnt.value].cpu().numpy()

@@ -353,9 +353,16 @@ def test_sort_sizes_vs_oracle(ex, orc, n):
 @pytest.mark.parametrize("kind", ["dups", "const", "small_range", "extremes", "negative", "unaligned",
                                   "skewed", "sparse_digits", "top_and_bottom"])
 def test_sort_distributions(ex, orc, kind, n):
-    """Distributions that drive the MSD sort (msd_sort.hip) through every branch: segments
-    of equal keys larger than a local sort (copied), digits constant inside a segment but
-    not globally (pass-through levels), varying digits that are not adjacent."""
+    """Named distributions at 3e5 and 3e6 keys, bit-exact against the oracle.  What they reach
+    in msd_sort.hip (followed through msd_sort_i64; nothing here checks which path ran):
+    `const` ends after the first histogram and `dups` after one rebased scatter level, both
+    as runs of equal keys in ms_copy_kernel (neither reaches a local sort or its LSD
+    fallback); `extremes` takes the device-planned pass-through levels (digits constant
+    inside a segment) down to bit 0; `small_range` the rebased first digit; `sparse_digits`
+    and `top_and_bottom` (varying digits that are not adjacent) leave segments of few
+    distinct keys, where the fallback can be reached.  The window networks above 16 keys,
+    the fallback in every size class, segments with fewer varying bits than bucket bits and
+    the tile edges are driven on purpose by test_gpu_sort_paths.py."""
     rng = np.random.default_rng(9)
     if kind == "dups":
         v = rng.integers(-50, 50, n).astype(np.int64)

@@ -4,44 +4,15 @@ while projecting other columns): nut_sort_pairs (stable key + row id sort) and S
 that gather their projected columns through the sorted row ids.  Parity: numpy's stable
 argsort / lexsort over the same keys — row ids and gathered values bit-exact, ties in
 row order (the implementation is stable; SQL allows any tie order, the test pins ours)."""
-import ctypes as C
-
 import numpy as np
 import pytest
-import torch
+
+from helpers import dev, sort_pairs, topk_positions, ukey
 
 pytestmark = pytest.mark.gpu
 
 I64_MIN = np.iinfo(np.int64).min
 I64_MAX = np.iinfo(np.int64).max
-
-
-def dev(x, ex):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(ex.device)
-
-
-def ukey(v, desc=False):
-    """The sort's unsigned order key: int64 sign-flipped, float64 by the IEEE total order."""
-    b = np.ascontiguousarray(v).view(np.uint64)
-    if v.dtype == np.float64:
-        u = np.where(b >> np.uint64(63), ~b, b | np.uint64(1 << 63))
-    else:
-        u = b ^ np.uint64(1 << 63)
-    return ~u if desc else u
-
-
-def sort_pairs(ex, keys, desc=False, vals=None):
-    from nutdb_amd._lib import T_F64, T_I64, check, lib
-    n = len(keys)
-    k = dev(keys, ex)
-    v = dev(vals, ex) if vals is not None else None
-    out = torch.empty(max(n, 1), dtype=torch.int64, device=ex.device)
-    ex._bind_stream()
-    check(lib.nut_sort_pairs(ex.ctx, C.c_void_p(k.data_ptr() if n else None), T_F64 if keys.dtype == np.float64 else T_I64,
-                             int(desc), C.c_void_p(v.data_ptr()) if v is not None else None,
-                             C.c_void_p(out.data_ptr()), n), "nut_sort_pairs")
-    ex.sync()
-    return out[:n].cpu().numpy()
 
 
 @pytest.mark.parametrize("n", [0, 1, 7, 8192, 8193, 100_003, 3_000_001])
@@ -151,20 +122,6 @@ def test_sql_order_by_string_key_rejected(ex):
 
 
 # ------------------------------------------------------------------ ORDER BY ... LIMIT (top-k)
-def topk_positions(ex, keys, k, desc=False, cap=None):
-    from nutdb_amd._lib import T_F64, T_I64, lib
-    n = len(keys)
-    d = dev(keys, ex)
-    cap = n if cap is None else cap
-    out = torch.empty(max(cap, 1), dtype=torch.int64, device=ex.device)
-    cnt = C.c_uint64()
-    ex._bind_stream()
-    st = lib.nut_topk_positions(ex.ctx, C.c_void_p(d.data_ptr()), T_F64 if keys.dtype == np.float64 else T_I64,
-                                1 if desc else 0, n, k, C.c_void_p(out.data_ptr()), cap, C.byref(cnt))
-    ex.sync()
-    return st, cnt.value, out[: cnt.value].cpu().numpy()
-
-
 @pytest.mark.parametrize("desc", [False, True])
 @pytest.mark.parametrize("kind", ["uniform", "narrow", "ties", "f64"])
 def test_topk_positions(ex, kind, desc):
