@@ -510,6 +510,16 @@ void nut_join_free(nut_join *j);
 nut_status nut_join_i64_into(nut_ctx *ctx, const int64_t *build, uint64_t nbuild, const int64_t *probe,
                              uint64_t nprobe, int join_type, int64_t *probe_idx, int64_t *build_idx, uint64_t cap,
                              uint64_t *npairs);
+/* The layout of the join's hash table for `nbuild` build rows (host only: no context, no
+ * device, nothing runs): *capacity slots (a power of two, >= 2 x nbuild, >= 64); `key`'s
+ * home slot *home, from which its run is probed linearly; runs wrap inside aligned blocks
+ * of *wrap_block slots — the whole table, or with region_built != 0 one region of a table
+ * built region by region (NUT_OPT_JOIN_REGION; NUT_ERR_INVALID_ARG when a table of this
+ * capacity has no regions); a region has *region_slots slots and is built that way only
+ * while no region holds more than *region_limit build rows.  A test hook: tests compute
+ * keys with chosen home slots from it. */
+nut_status nut_join_layout(uint64_t nbuild, int64_t key, int region_built, uint64_t *capacity, uint64_t *home,
+                           uint64_t *wrap_block, uint64_t *region_slots, uint64_t *region_limit);
 /* Expression-mode scan + compaction: the row ids (ascending) of the
  * rows where s->where holds — any program over s->prog_col, compiled for the query like
  * the expression-mode group-by.  Reads s->n, s->where and the program columns only (keys

@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "hj_layout.hpp"
 #include "lookback.hpp"
 #include "sort.hpp"
 
@@ -52,17 +53,9 @@ struct HjTable {
   int shift;       // 64 - log2(capacity)
 };
 
-// home hash = mix64(key ^ 0x3C6EF372FE94F82A), written as the group-by's owner hash of a
-// re-keyed key so the partition kernels (gpart.hpp, kx) compute the same digits; it is
-// independent of the multi-GPU owner (owner_hash of the key itself)
-constexpr uint64_t HJ_KX = 0x6A09E667F3BCC908ull ^ 0x3C6EF372FE94F82Aull;
-
-__device__ __forceinline__ uint64_t hj_home(int64_t k, const HjTable &t) {
-  return owner_hash((uint64_t)k ^ HJ_KX, 0, 1) >> t.shift;
-}
-__device__ __forceinline__ uint64_t hj_next(uint64_t s, const HjTable &t) {
-  return (s & ~t.wmask) | ((s + 1) & t.wmask);
-}
+// the layout arithmetic (home hash, wrap rule, capacity, regions) is hj_layout.hpp's
+__device__ __forceinline__ uint64_t hj_home(int64_t k, const HjTable &t) { return hj_home_slot(k, t.shift); }
+__device__ __forceinline__ uint64_t hj_next(uint64_t s, const HjTable &t) { return hj_next_slot(s, t.wmask); }
 
 // Build and duplicate check: HJ_BITEMS rows per lane in flight (their slot atomics /
 // loads are issued together each round, like the probe's run walks).
@@ -155,11 +148,10 @@ __global__ __launch_bounds__(256) void hj_dupcheck_kernel(const int64_t *__restr
 // duplicate keys, and writes it out whole (the table needs no memset).  Persistent (one
 // workgroup per CU, nreg / grid regions each): the next region's records are loaded
 // before this region's write-out, so their latency hides behind its 128 KB of stores.
-constexpr uint32_t HJ_RS = 8192;
 constexpr int HJ_RTHREADS = 1024;
 
-// records per lane: the host sends a region at most 7/8 x HJ_RS records
-constexpr int HJ_RK = (HJ_RS * 7 / 8 + HJ_RTHREADS - 1) / HJ_RTHREADS;
+// records per lane: the host sends a region at most HJ_RLIMIT = 7/8 x HJ_RS records
+constexpr int HJ_RK = (HJ_RLIMIT + HJ_RTHREADS - 1) / HJ_RTHREADS;
 
 __global__ __launch_bounds__(HJ_RTHREADS) void hj_region_build_kernel(const int64_t *__restrict__ keys,
                                                                       const int64_t *__restrict__ rows,
@@ -569,8 +561,7 @@ namespace {
 
 nut_status join_build(nut_ctx *c, nut_join *j, const int64_t *build, uint64_t nb) {
   hipStream_t st = c->stream;
-  int log2c = 6;  // >= 2 slots per build row, >= 64 slots
-  while ((1ull << log2c) < 2 * nb) ++log2c;
+  const int log2c = hj_log2_capacity(nb);  // >= 2 slots per build row, >= 64 slots
   const uint64_t cap = 1ull << log2c;
   j->cfg = (int)c->opt[NUT_OPT_JOIN_PROBE_CFG];
   j->any_cfg = (int)c->opt[NUT_OPT_JOIN_ANY_CFG];
@@ -592,7 +583,7 @@ nut_status join_build(nut_ctx *c, nut_join *j, const int64_t *build, uint64_t nb
   // region build for tables of 2^22 .. 2^29 slots (regions of 8192 slots, one 16-bit
   // partition), unless a region would be too full (many equal keys): then global CAS
   const bool region_on = c->opt[NUT_OPT_JOIN_REGION] != 0;
-  if (nb && region_on && log2c >= 22 && log2c <= 29) {
+  if (nb && region_on && hj_has_regions(log2c)) {
     const int rb = log2c - 13;
     const uint64_t nreg = 1ull << rb;
     int64_t *tmp = nullptr;
@@ -611,7 +602,7 @@ nut_status join_build(nut_ctx *c, nut_join *j, const int64_t *build, uint64_t nb
       off[r + 1] = off[r] + cnt;
       mx = std::max(mx, cnt);
     }
-    if (mx <= HJ_RS * 7 / 8) {
+    if (mx <= HJ_RLIMIT) {
       uint64_t *doff = nullptr;
       NUT_HIP(hipMallocAsync((void **)&doff, (nreg + 1) * 8, st));
       NUT_HIP(hipMemcpyAsync(doff, off.data(), (nreg + 1) * 8, hipMemcpyHostToDevice, st));
@@ -810,6 +801,23 @@ nut_status nut_join_write(nut_join *j, int64_t *probe_idx, int64_t *build_idx) {
 nut_status nut_join_i64_into(nut_ctx *c, const int64_t *build, uint64_t nb, const int64_t *probe, uint64_t np,
                              int type, int64_t *probe_idx, int64_t *build_idx, uint64_t cap, uint64_t *npairs) {
   return join_i64_into_rows(c, build, nullptr, nb, probe, nullptr, np, type, probe_idx, build_idx, cap, npairs);
+}
+
+// host only: the layout join_build gives a table of nb build rows, and `key`'s place in it
+nut_status nut_join_layout(uint64_t nb, int64_t key, int region_built, uint64_t *capacity, uint64_t *home,
+                           uint64_t *wrap_block, uint64_t *region_slots, uint64_t *region_limit) {
+  if (!capacity || !home || !wrap_block || !region_slots || !region_limit)
+    return fail(NUT_ERR_INVALID_ARG, "nut_join_layout: NULL argument");
+  if (nb >= (1ull << 31)) return fail(NUT_ERR_UNSUPPORTED, "nut_join_layout: build side >= 2^31 rows");
+  const int log2c = hj_log2_capacity(nb);
+  if (region_built && !hj_has_regions(log2c))
+    return fail(NUT_ERR_INVALID_ARG, "nut_join_layout: a table of 2^" + std::to_string(log2c) + " slots has no regions");
+  *capacity = 1ull << log2c;
+  *home = hj_home_slot(key, 64 - log2c);
+  *wrap_block = region_built ? (uint64_t)HJ_RS : *capacity;
+  *region_slots = HJ_RS;
+  *region_limit = HJ_RLIMIT;
+  return NUT_OK;
 }
 
 void nut_join_free(nut_join *j) {
