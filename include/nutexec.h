@@ -298,7 +298,33 @@ typedef enum {
  *            d - fmod(d + 3, 7), WEEK_SUNDAY = d - fmod(d + 4, 7); MONTH, QUARTER, YEAR = the
  *            first day of d's month, quarter, year; MONTH_END = the last day of d's month
  *   ADDMONTHS pops d (days), n (months): the day number of the proleptic Gregorian date n
- *            months from d, the day of month clamped to the target month's length */
+ *            months from d, the day of month clamped to the target month's length
+ * The math ops below never set an error.  "quieted" = the NaN's bits | 0x0008000000000000;
+ * "the negative quiet NaN" = 0xFFF8000000000000 (what 0 / 0 gives).
+ *   FLOOR CEIL TRUNC ROUND  one operand; arg = the digit count N, a literal in [-18, 18].
+ *            f64 operand, f64 result: N = 0: IEEE floor / ceil / trunc / round-half-to-even;
+ *            N > 0: op(x * 10^N) / 10^N; N < 0: op(x / 10^-N) * 10^-N, each step its own IEEE
+ *            operation; a scaled intermediate that is not finite gives x; a NaN passes
+ *            quieted, +-inf and +-0.0 pass, ceil(-0.5) = -0.0.
+ *            int / bool operand, int result: N >= 0 is the identity; N < 0, m = 10^-N: the
+ *            multiple of m below (FLOOR), above (CEIL), toward zero (TRUNC), nearest with ties
+ *            away from zero (ROUND); a result outside int64 wraps as the int * does
+ *   MATH     one operand converted to f64, f64 result, by arg (nut_math_fn): SQRT (correctly
+ *            rounded), EXP, LN, LOG2, LOG10 (the math library's, within 3 ulp)
+ *   POW      pops x, y converted to f64: x to the power y (C99 special cases: pow(x, +-0) = 1
+ *            and pow(1, y) = 1 also for a NaN; within 16 ulp)
+ *            MATH and POW: a NaN operand passes quieted, the first operand's first; an invalid
+ *            operation (sqrt(-1), ln(-1), pow(-8, 0.5)) gives the negative quiet NaN;
+ *            ln / log2 / log10 of +-0 = -inf
+ *   SIGN     one operand, int result -1 / 0 / 1; NaN and +-0.0 give 0
+ *   LEAST GREATEST  pop a, b: both int / bool: int result; else both compare as f64, f64
+ *            result: a NaN operand gives that NaN quieted, the first operand's first; equal
+ *            operands (+-0.0 included) give the first
+ *   CAST     one operand, by arg (nut_cast).  TO_I64: an f64 truncates toward zero, saturates
+ *            at INT64_MIN / INT64_MAX, NaN gives 0; an int / bool is itself.  TO_I32 .. TO_U8:
+ *            TO_I64 first, then the low 32 / 16 / 8 bits sign- or zero-extended (an int result
+ *            word).  TO_F32, f64 result: the operand rounded to nearest even to binary32 (an
+ *            int directly, not through f64) and widened back; a NaN passes quieted */
 typedef enum {
   NUT_P_COL = 0, NUT_P_I64 = 1, NUT_P_F64 = 2,
   NUT_P_ADD = 3, NUT_P_SUB = 4, NUT_P_MUL = 5, NUT_P_DIV = 6, NUT_P_MOD = 7, NUT_P_INTDIV = 8,
@@ -307,8 +333,17 @@ typedef enum {
   NUT_P_BITAND = 19, NUT_P_BITOR = 20, NUT_P_BITXOR = 21, NUT_P_BITNOT = 22,
   NUT_P_SHL = 23, NUT_P_SHR = 24,
   NUT_P_IF = 25, NUT_P_ABS = 26, NUT_P_TO_F64 = 27, NUT_P_LOOKUP = 28, NUT_P_DATEPART = 29,
-  NUT_P_MAP = 30, NUT_P_TIMEPART = 31, NUT_P_DATETRUNC = 32, NUT_P_ADDMONTHS = 33
+  NUT_P_MAP = 30, NUT_P_TIMEPART = 31, NUT_P_DATETRUNC = 32, NUT_P_ADDMONTHS = 33,
+  /* (34 is not assigned: it stays the unknown op it has always been) */
+  NUT_P_FLOOR = 35, NUT_P_CEIL = 36, NUT_P_TRUNC = 37, NUT_P_ROUND = 38, NUT_P_MATH = 39, NUT_P_POW = 40,
+  NUT_P_SIGN = 41, NUT_P_LEAST = 42, NUT_P_GREATEST = 43, NUT_P_CAST = 44
 } nut_prog_op;
+typedef enum { NUT_MF_SQRT = 0, NUT_MF_EXP = 1, NUT_MF_LN = 2, NUT_MF_LOG2 = 3, NUT_MF_LOG10 = 4 } nut_math_fn;
+typedef enum {
+  NUT_CAST_I64 = 0, NUT_CAST_I32 = 1, NUT_CAST_I16 = 2, NUT_CAST_I8 = 3,
+  NUT_CAST_U32 = 4, NUT_CAST_U16 = 5, NUT_CAST_U8 = 6, NUT_CAST_F32 = 7
+} nut_cast;
+#define NUT_MAX_ROUND_DIGITS 18
 typedef enum {
   NUT_DP_YEAR = 0, NUT_DP_MONTH = 1, NUT_DP_DAY = 2, NUT_DP_QUARTER = 3, NUT_DP_WEEKDAY = 4, NUT_DP_YEARDAY = 5,
   NUT_DP_YYYYMM = 6, NUT_DP_YYYYMMDD = 7, NUT_DP_REL_MONTH = 8, NUT_DP_REL_QUARTER = 9, NUT_DP_REL_WEEK = 10
@@ -325,7 +360,8 @@ typedef enum { NUT_PT_I64 = 0, NUT_PT_F64 = 1, NUT_PT_BOOL = 2 } nut_prog_value_
 typedef struct {
   int32_t op;   /* nut_prog_op */
   int32_t arg;  /* NUT_P_COL: column index; NUT_P_LOOKUP / MAP: table length;
-                   NUT_P_DATEPART / TIMEPART / DATETRUNC: the part (nut_date_part / nut_time_part / nut_date_trunc) */
+                   NUT_P_DATEPART / TIMEPART / DATETRUNC: the part (nut_date_part / nut_time_part / nut_date_trunc);
+                   NUT_P_FLOOR / CEIL / TRUNC / ROUND: the digit count N; NUT_P_MATH: nut_math_fn; NUT_P_CAST: nut_cast */
   int64_t v;    /* NUT_P_I64 / NUT_P_F64 constant; NUT_P_LOOKUP / MAP: table address */
 } nut_prog_node;
 typedef struct {

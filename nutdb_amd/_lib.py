@@ -52,7 +52,8 @@ EX_COL, EX_MUL, EX_ADD, EX_SUB, EX_MUL_1M, EX_MUL_1M_1P = range(6)
 # nut_prog_op (expression programs, RPN) and nut_prog_value_type
 PROG_OPS = ["col", "i64", "f64", "add", "sub", "mul", "div", "mod", "intdiv", "lt", "le", "gt", "ge", "eq", "ne",
             "and", "or", "xor", "not", "bitand", "bitor", "bitxor", "bitnot", "shl", "shr", "if", "abs", "to_f64", "lookup",
-            "datepart", "map", "timepart", "datetrunc", "addmonths"]
+            "datepart", "map", "timepart", "datetrunc", "addmonths", None, "floor", "ceil", "trunc", "round", "math", "pow",
+            "sign", "least", "greatest", "cast"]
 # nut_date_part (the arg of a "datepart" node)
 DP_YEAR, DP_MONTH, DP_DAY, DP_QUARTER, DP_WEEKDAY, DP_YEARDAY, DP_YYYYMM, DP_YYYYMMDD = range(8)
 DP_REL_MONTH, DP_REL_QUARTER, DP_REL_WEEK = 8, 9, 10
@@ -61,7 +62,12 @@ DP_REL_MONTH, DP_REL_QUARTER, DP_REL_WEEK = 8, 9, 10
  TP_START_HOUR, TP_START_DAY) = range(9)
 # nut_date_trunc (the arg of a "datetrunc" node: its operand is days)
 DT_WEEK_MONDAY, DT_WEEK_SUNDAY, DT_MONTH, DT_QUARTER, DT_YEAR, DT_MONTH_END = range(6)
-P = {name: i for i, name in enumerate(PROG_OPS)}
+# nut_math_fn (the arg of a "math" node) and nut_cast (the arg of a "cast" node); the arg of
+# "floor" / "ceil" / "trunc" / "round" is the digit count N in [-18, 18]
+MF_SQRT, MF_EXP, MF_LN, MF_LOG2, MF_LOG10 = range(5)
+CAST_I64, CAST_I32, CAST_I16, CAST_I8, CAST_U32, CAST_U16, CAST_U8, CAST_F32 = range(8)
+MAX_ROUND_DIGITS = 18
+P = {name: i for i, name in enumerate(PROG_OPS) if name}  # (op 34 is not assigned)
 PT_I64, PT_F64, PT_BOOL = 0, 1, 2
 
 

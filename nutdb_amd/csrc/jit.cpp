@@ -76,7 +76,7 @@ struct Gen {
       PVal a[3];
       const int op = nd.op;
       const int arity = prog_arity(op);
-      if (op < 0 || op > NUT_P_ADDMONTHS) return fail("unknown program op " + std::to_string(op));
+      if (op < 0 || op > NUT_P_CAST || (op > NUT_P_ADDMONTHS && op < NUT_P_FLOOR)) return fail("unknown program op " + std::to_string(op));
       if (!pop(arity, a)) return fail("program stack underflow at node " + std::to_string(i));
       PVal r;
       const bool f = arity == 2 && (a[0].t == NUT_PT_F64 || a[1].t == NUT_PT_F64);
@@ -195,6 +195,49 @@ struct Gen {
           if (f) return fail("ADDMONTHS needs integer operands (days, months)");
           r = {NUT_PT_I64, "jaddmonths(" + as_i(a[0]) + ", " + as_i(a[1]) + ")"};
           break;
+        case NUT_P_FLOOR:
+        case NUT_P_CEIL:
+        case NUT_P_TRUNC:
+        case NUT_P_ROUND: {
+          static const char *nm[] = {"FLOOR", "CEIL", "TRUNC", "ROUND"};
+          const int m = op - NUT_P_FLOOR;
+          if (nd.arg < -NUT_MAX_ROUND_DIGITS || nd.arg > NUT_MAX_ROUND_DIGITS)
+            return fail(std::string(nm[m]) + ": digit count " + std::to_string(nd.arg) + " is outside [-18, 18]");
+          // (m and N are literals of the source: an integer's divisor 10^-N folds to one)
+          const std::string lit = ", " + std::to_string(m) + ", " + std::to_string(nd.arg) + ")";
+          if (a[0].t == NUT_PT_F64) r = {NUT_PT_F64, "jroundf(" + a[0].s + lit};
+          else if (nd.arg >= 0) r = {NUT_PT_I64, as_i(a[0])};
+          else r = {NUT_PT_I64, "jroundi(" + as_i(a[0]) + lit};
+          break;
+        }
+        case NUT_P_MATH: {
+          static const char *fn[] = {"jsqrt(", "jexp(", "jln(", "jlog2(", "jlog10("};
+          if (nd.arg < NUT_MF_SQRT || nd.arg > NUT_MF_LOG10) return fail("MATH: unknown function " + std::to_string(nd.arg));
+          r = {NUT_PT_F64, fn[nd.arg] + as_f(a[0]) + ")"};
+          break;
+        }
+        case NUT_P_POW: r = {NUT_PT_F64, "jpow(" + as_f(a[0]) + ", " + as_f(a[1]) + ")"}; break;
+        case NUT_P_SIGN:
+          r = {NUT_PT_I64, a[0].t == NUT_PT_F64 ? "jsignf(" + a[0].s + ")" : "jsigni(" + as_i(a[0]) + ")"};
+          break;
+        case NUT_P_LEAST:
+        case NUT_P_GREATEST: {
+          const std::string nm = op == NUT_P_LEAST ? "jleast" : "jgreatest";
+          if (f) r = {NUT_PT_F64, nm + "f(" + as_f(a[0]) + ", " + as_f(a[1]) + ")"};
+          else r = {NUT_PT_I64, nm + "i(" + as_i(a[0]) + ", " + as_i(a[1]) + ")"};
+          break;
+        }
+        case NUT_P_CAST: {
+          if (nd.arg < NUT_CAST_I64 || nd.arg > NUT_CAST_F32) return fail("CAST: unknown target " + std::to_string(nd.arg));
+          const bool fl = a[0].t == NUT_PT_F64;
+          if (nd.arg == NUT_CAST_F32) {
+            r = {NUT_PT_F64, fl ? "jtof32(" + a[0].s + ")" : "jtof32i(" + as_i(a[0]) + ")"};
+            break;
+          }
+          const std::string w = fl ? "jtoi64(" + a[0].s + ")" : as_i(a[0]);
+          r = {NUT_PT_I64, nd.arg == NUT_CAST_I64 ? w : "jnarrow(" + w + ", " + std::to_string(nd.arg) + ")"};
+          break;
+        }
       }
       if (r.s.size() > (1u << 20)) return fail("expression program too large");
       st.push_back(std::move(r));
@@ -214,7 +257,7 @@ typedef unsigned short uint16_t;
 typedef unsigned char uint8_t;
 #include "agg_kernel.hpp"
 #include "select_kernel.hpp"
-#include "prog_ops.hpp"  // the integer and calendar helpers (jdiv ... jaddmonths)
+#include "prog_ops.hpp"  // the integer, calendar and exact math helpers (jdiv ... jtof32)
 namespace nut {
 // f64 MOD: C fmod with the NaN rule of f64 DIV on this device (include/nutexec.h): a NaN
 // operand passes through quieted, the first operand's first; an invalid operation (x mod 0,
@@ -222,6 +265,24 @@ namespace nut {
 // +qNaN for all of these, and MIN / MAX order NaNs by sign.
 __device__ __forceinline__ double jfmod(double a, double b) {
   const double r = fmod(a, b);
+  if (r == r) return r;
+  if (a != a) return as_f64(as_u64(a) | 0x0008000000000000ull);
+  if (b != b) return as_f64(as_u64(b) | 0x0008000000000000ull);
+  return as_f64(0xFFF8000000000000ull);
+}
+// exp, ln, log2, log10 and pow: the device library's, with the same NaN rule (a NaN operand
+// passes quieted, the first operand's first; an invalid operation gives the negative quiet
+// NaN).  pow(x, 0) and pow(1, y) are 1 for a NaN too (C99), so the result decides.
+__device__ __forceinline__ double jnan1(double r, double a) {
+  if (r == r) return r;
+  return a != a ? as_f64(as_u64(a) | 0x0008000000000000ull) : as_f64(0xFFF8000000000000ull);
+}
+__device__ __forceinline__ double jexp(double a) { return jnan1(exp(a), a); }
+__device__ __forceinline__ double jln(double a) { return jnan1(log(a), a); }
+__device__ __forceinline__ double jlog2(double a) { return jnan1(log2(a), a); }
+__device__ __forceinline__ double jlog10(double a) { return jnan1(log10(a), a); }
+__device__ __forceinline__ double jpow(double a, double b) {
+  const double r = pow(a, b);
   if (r == r) return r;
   if (a != a) return as_f64(as_u64(a) | 0x0008000000000000ull);
   if (b != b) return as_f64(as_u64(b) | 0x0008000000000000ull);

@@ -1,4 +1,4 @@
-// prog_ops.hpp — the one definition of the integer and calendar semantics of the nut_prog
+// prog_ops.hpp — the one definition of the integer, calendar and exact math semantics of the nut_prog
 // ops (include/nutexec.h, nut_prog_op), and of every op's arity.
 //
 // Compiled three ways from this one text: by hipRTC inside the generated scan kernels
@@ -31,7 +31,14 @@ NUT_OPFN int prog_arity(int op) {
     case NUT_P_MAP:
     case NUT_P_DATEPART:
     case NUT_P_TIMEPART:
-    case NUT_P_DATETRUNC: return 1;
+    case NUT_P_DATETRUNC:
+    case NUT_P_FLOOR:
+    case NUT_P_CEIL:
+    case NUT_P_TRUNC:
+    case NUT_P_ROUND:
+    case NUT_P_MATH:
+    case NUT_P_SIGN:
+    case NUT_P_CAST: return 1;
     case NUT_P_IF: return 3;
     default: return 2;
   }
@@ -154,5 +161,98 @@ NUT_OPFN int64_t jaddmonths(int64_t d, int64_t n) {
   const uint32_t md = jmonth_days(yr, m);
   return jdays(e * 400, yr, m, c.d < md ? c.d : md);
 }
+
+// ---- rounding, sign, least / greatest, casts, sqrt (include/nutexec.h: every result here is
+// exactly defined, so host and device agree bit for bit).  Compiler builtins only.
+NUT_OPFN uint64_t jbits(double x) {
+  uint64_t u;
+  __builtin_memcpy(&u, &x, 8);
+  return u;
+}
+NUT_OPFN double jdbl(uint64_t u) {
+  double x;
+  __builtin_memcpy(&x, &u, 8);
+  return x;
+}
+NUT_OPFN double jquiet(double x) { return jdbl(jbits(x) | 0x0008000000000000ull); }
+NUT_OPFN double jnegnan() { return jdbl(0xFFF8000000000000ull); }
+// 10^n, 0 <= n <= 18: a literal n folds to a literal (the divisions below then compile to
+// multiplies and shifts, as the calendar's do)
+NUT_OPFN int64_t jpow10(const int n) {
+  int64_t m = 1;
+  for (int i = 0; i < 18; ++i)
+    if (i < n) m *= 10;
+  return m;
+}
+// M: 0 floor, 1 ceil, 2 trunc, 3 round (half to even)
+NUT_OPFN double jround0(double x, const int M) {
+  return M == 0 ? __builtin_floor(x) : M == 1 ? __builtin_ceil(x) : M == 2 ? __builtin_trunc(x) : __builtin_rint(x);
+}
+// N digits after (N > 0) or before (N < 0) the point; every step one IEEE operation
+NUT_OPFN double jroundf(double x, const int M, const int N) {
+  if (x != x) return jquiet(x);
+  if (N == 0) return jround0(x, M);
+  const double s = (double)jpow10(N < 0 ? -N : N);  // exact: 10^18 < 2^63 and 5^18 < 2^53
+  const double t = N > 0 ? x * s : x / s;
+  if (t - t != 0.0) return x;  // the scaled value is not finite
+  const double r = jround0(t, M);
+  return N > 0 ? r / s : r * s;
+}
+// N < 0: to a multiple of m = 10^-N; ROUND: ties away from zero.  Wraps as the int * does.
+NUT_OPFN int64_t jroundi(int64_t x, const int M, const int N) {
+  if (N >= 0) return x;
+  const int64_t m = jpow10(-N);
+  const int64_t q = x / m, r = x - q * m;  // toward zero; r has the sign of x, |r| < m <= 10^18
+  const uint64_t t = (uint64_t)(q * m);
+  if (M == 0) return (int64_t)(r < 0 ? t - (uint64_t)m : t);
+  if (M == 1) return (int64_t)(r > 0 ? t + (uint64_t)m : t);
+  if (M == 2) return (int64_t)t;
+  if (r >= 0) return (int64_t)(2 * r >= m ? t + (uint64_t)m : t);
+  return (int64_t)(-2 * r >= m ? t - (uint64_t)m : t);
+}
+NUT_OPFN double jsqrt(double x) {
+  if (x != x) return jquiet(x);
+  if (x < 0.0) return jnegnan();
+  return __builtin_sqrt(x);
+}
+NUT_OPFN int64_t jsignf(double x) { return x > 0.0 ? 1 : x < 0.0 ? -1 : 0; }
+NUT_OPFN int64_t jsigni(int64_t x) { return x > 0 ? 1 : x < 0 ? -1 : 0; }
+NUT_OPFN int64_t jleasti(int64_t a, int64_t b) { return b < a ? b : a; }
+NUT_OPFN int64_t jgreatesti(int64_t a, int64_t b) { return b > a ? b : a; }
+NUT_OPFN double jleastf(double a, double b) {
+  if (a != a) return jquiet(a);
+  if (b != b) return jquiet(b);
+  return b < a ? b : a;
+}
+NUT_OPFN double jgreatestf(double a, double b) {
+  if (a != a) return jquiet(a);
+  if (b != b) return jquiet(b);
+  return b > a ? b : a;
+}
+// f64 -> int64: toward zero, saturating, NaN = 0 (clamped before the conversion: no value
+// reaches it that it does not define)
+NUT_OPFN int64_t jtoi64(double x) {
+  if (x != x) return 0;
+  if (x >= 9223372036854775808.0) return (int64_t)0x7FFFFFFFFFFFFFFFll;
+  if (x <= -9223372036854775808.0) return (int64_t)(-0x7FFFFFFFFFFFFFFFll - 1);
+  return (int64_t)x;
+}
+// C = nut_cast (I64 .. U8): the low bits, sign- or zero-extended
+NUT_OPFN int64_t jnarrow(int64_t v, const int C) {
+  const uint64_t u = (uint64_t)v;
+  if (C == 1) return (int64_t)(int32_t)(uint32_t)u;
+  if (C == 2) return (int64_t)(short)(uint16_t)u;
+  if (C == 3) return (int64_t)(signed char)(uint8_t)u;
+  if (C == 4) return (int64_t)(uint32_t)u;
+  if (C == 5) return (int64_t)(uint16_t)u;
+  if (C == 6) return (int64_t)(uint8_t)u;
+  return v;
+}
+// to binary32 (nearest even; beyond its range: +-inf) and back
+NUT_OPFN double jtof32(double x) {
+  if (x != x) return jquiet(x);
+  return (double)(float)x;
+}
+NUT_OPFN double jtof32i(int64_t x) { return (double)(float)x; }
 
 }  // namespace nut

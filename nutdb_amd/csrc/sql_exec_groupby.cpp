@@ -293,6 +293,11 @@ XVal xpr_eval(const XNode &x, const std::vector<std::vector<uint64_t>> &cols, co
   }
   const XVal a = xpr_eval(x.kids[0], cols, types, g, div0);
   if (x.k == X_ABS) return a.is_int ? XVal{true, jabs(a.i), 0.0} : XVal{false, 0, fabs(a.f)};
+  if (x.k == X_FN) {  // a math op: prog_ops.hpp's functions (math_apply)
+    const XVal b = x.kids.size() > 1 ? xpr_eval(x.kids[1], cols, types, g, div0) : a;
+    const MVal r = math_apply(x.op, x.arg, MVal{a.is_int, a.i, a.f}, MVal{b.is_int, b.i, b.f});
+    return XVal{r.is_int, r.i, r.f};
+  }
   if (x.k == X_TOF) return XVal{false, 0, a.as_f()};
   const XVal b = xpr_eval(x.kids[1], cols, types, g, div0);
   const bool ii = a.is_int && b.is_int;
@@ -322,6 +327,13 @@ int xpr_type(const XNode &x, const std::vector<int> &types) {
     for (const XNode &k : x.kids)
       if (xpr_type(k, types) < 0) return -1;
     return NUT_T_F64;
+  }
+  if (x.k == X_FN) {
+    int tk[2] = {NUT_T_I64, NUT_T_I64};
+    for (size_t i = 0; i < x.kids.size() && i < 2; ++i)
+      if ((tk[i] = xpr_type(x.kids[i], types)) < 0) return -1;
+    if (x.kids.size() < 2) tk[1] = tk[0];
+    return math_is_int(x.op, x.arg, tk[0] != NUT_T_F64, tk[1] != NUT_T_F64) ? NUT_T_I64 : NUT_T_F64;
   }
   int t = NUT_T_I64;
   for (const XNode &k : x.kids) {

@@ -478,6 +478,8 @@ nut_status check_strings(const nut_plan &p, const PProg &pp, const Dict *const *
     if ((op == NUT_P_EQ || op == NUT_P_NE) && a[0] && a[1] && a[0] != kConst && a[1] != kConst && a[0] != a[1])
       return fail(NUT_ERR_PLAN, std::string(what) + ": string columns of two tables compared (their dictionaries "
                                                     "differ; only columns of one table compare)");
+    if (math_op(op) && (a[0] || a[1]))
+      return fail(NUT_ERR_PLAN, std::string(what) + ": '" + n.c.s + "' takes numbers, not strings");
     if (!(op == NUT_P_EQ || op == NUT_P_NE) && (a[0] || a[1] || a[2]))
       return fail(NUT_ERR_PLAN, std::string(what) + ": strings are executed in = / != / IN and as GROUP BY keys only");
     st.push_back(nullptr);
@@ -666,7 +668,8 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
       };
       std::vector<KVal> ks;
       for (const PNode &n : pp) {
-        const bool part = n.op == NUT_P_DATEPART || n.op == NUT_P_TIMEPART || n.op == NUT_P_DATETRUNC;
+        // (nodes whose arg is a literal of the op: a calendar part, a digit count, a function)
+        const bool part = n.op == NUT_P_DATEPART || n.op == NUT_P_TIMEPART || n.op == NUT_P_DATETRUNC || math_op(n.op);
         nut_prog_node q{n.op, part ? n.arg : 0, 0};
         KVal a[3] = {{K_PLAIN, v.size()}, {K_PLAIN, v.size()}, {K_PLAIN, v.size()}};
         const int ar = pnode_arity(n.op);

@@ -75,6 +75,25 @@ void json_str(std::string &o, sv s) {
 
 
 
+// exact decimal of a finite double (17 significant digits: strtod gives the double back)
+Decimal decimal_of(double d) {
+  Decimal x;
+  if (d == 0.0) return x;
+  char buf[64];
+  snprintf(buf, sizeof buf, "%.16e", d);  // [-]d.dddddddddddddddde[+-]XX
+  const char *q = buf;
+  if (*q == '-') x.neg = true, ++q;
+  std::string digs;
+  for (; *q && *q != 'e'; ++q)
+    if (*q != '.') digs += *q;
+  const int64_t ex = strtoll(q + 1, nullptr, 10);
+  size_t z = 0;
+  while (z < digs.size() && digs[z] == '0') ++z;
+  x.digits = digs.substr(z);
+  x.scale = 16 - ex;
+  return x;
+}
+
 i128 sat_from_u128(u128 m, bool neg) {
   i128 v = m > (u128)kHuge ? kHuge : (i128)m;
   return neg ? -v : v;
@@ -281,7 +300,101 @@ bool const_int(const Expr &e, CVal &x, Lowering &L) {
 }  // namespace
 
 
+// SQL math functions (ClickHouse names) -> the program node
+bool math_fn(sv n, MathFn &f) {
+  static const struct {
+    const char *a, *b;
+    int op, arg, lo, hi;
+  } t[] = {{"floor", "", NUT_P_FLOOR, 0, 1, 2},         {"ceil", "ceiling", NUT_P_CEIL, 0, 1, 2},
+           {"trunc", "truncate", NUT_P_TRUNC, 0, 1, 2},  {"round", "", NUT_P_ROUND, 0, 1, 2},
+           {"sqrt", "", NUT_P_MATH, NUT_MF_SQRT, 1, 1},  {"exp", "", NUT_P_MATH, NUT_MF_EXP, 1, 1},
+           {"ln", "log", NUT_P_MATH, NUT_MF_LN, 1, 1},   {"log2", "", NUT_P_MATH, NUT_MF_LOG2, 1, 1},
+           {"log10", "", NUT_P_MATH, NUT_MF_LOG10, 1, 1}, {"pow", "power", NUT_P_POW, 0, 2, 2},
+           {"sign", "", NUT_P_SIGN, 0, 1, 1},            {"least", "", NUT_P_LEAST, 0, 2, 8},
+           {"greatest", "", NUT_P_GREATEST, 0, 2, 8},    {"toint64", "", NUT_P_CAST, NUT_CAST_I64, 1, 1},
+           {"toint32", "", NUT_P_CAST, NUT_CAST_I32, 1, 1},   {"toint16", "", NUT_P_CAST, NUT_CAST_I16, 1, 1},
+           {"toint8", "", NUT_P_CAST, NUT_CAST_I8, 1, 1},     {"touint32", "", NUT_P_CAST, NUT_CAST_U32, 1, 1},
+           {"touint16", "", NUT_P_CAST, NUT_CAST_U16, 1, 1},  {"touint8", "", NUT_P_CAST, NUT_CAST_U8, 1, 1},
+           {"tofloat32", "", NUT_P_CAST, NUT_CAST_F32, 1, 1}};
+  for (const auto &x : t)
+    if (ieq(n, x.a) || (*x.b && ieq(n, x.b))) {
+      f.op = x.op, f.arg = x.arg, f.lo = x.lo, f.hi = x.hi;
+      f.digits = x.op >= NUT_P_FLOOR && x.op <= NUT_P_ROUND;
+      return true;
+    }
+  return false;
+}
+// the function name describe() prints for a math node
+std::string math_text(int op, int arg) {
+  static const char *rn[] = {"floor", "ceil", "trunc", "round"};
+  static const char *mf[] = {"sqrt", "exp", "ln", "log2", "log10"};
+  static const char *cf[] = {"toInt64", "toInt32", "toInt16", "toInt8", "toUInt32", "toUInt16", "toUInt8", "toFloat32"};
+  if (op >= NUT_P_FLOOR && op <= NUT_P_ROUND) return rn[op - NUT_P_FLOOR];
+  if (op == NUT_P_MATH) return arg >= 0 && arg < 5 ? mf[arg] : "math";
+  if (op == NUT_P_CAST) return arg >= 0 && arg < 8 ? cf[arg] : "cast";
+  return op == NUT_P_POW ? "pow" : op == NUT_P_SIGN ? "sign" : op == NUT_P_LEAST ? "least" : "greatest";
+}
+// The shape of a math function call: argument count, and the digit count N of a rounding
+// (a constant integer in [-18, 18]); no string literal.  false with a message: a plan error
+// naming the call.
+bool math_call(const Expr &e, const MathFn &mf, int &digits, Lowering &L) {
+  const size_t na = e.kids.size();
+  digits = 0;
+  if ((int)na < mf.lo || (int)na > mf.hi)
+    return L.fail("'" + expr_text(e) + "': " + std::string(e.id.name) + " takes " +
+                  (mf.lo == mf.hi ? std::to_string(mf.lo) : std::to_string(mf.lo) + " to " + std::to_string(mf.hi)) +
+                  (mf.hi == 1 ? " argument" : " arguments") + (mf.digits ? " (a value and a constant digit count)" : ""));
+  if (mf.digits && na == 2) {
+    CVal d;
+    Lowering quiet;
+    if (!const_int(e.kids[1], d, quiet))
+      return L.fail("'" + expr_text(e) + "': the digit count of " + std::string(e.id.name) + " is a constant integer");
+    if (d.v < -NUT_MAX_ROUND_DIGITS || d.v > NUT_MAX_ROUND_DIGITS)
+      return L.fail("'" + expr_text(e) + "': the digit count " + i128_str(d.v) + " is outside [-18, 18]");
+    digits = (int)d.v;
+  }
+  for (size_t i = 0; i < (mf.digits ? 1 : na); ++i)
+    if (e.kids[i].k == EK::Literal && e.kids[i].lit->k == LitKind::String)
+      return L.fail("'" + expr_text(e) + "': " + std::string(e.id.name) + " takes numbers, not the string '" +
+                    e.kids[i].lit->str + "'");
+  return true;
+}
+// a numeric constant as a host operand of math_apply (an integer beyond int64: its double)
+bool const_num(const Expr &e, MVal &m, Lowering &L) {
+  CVal c;
+  if (!const_eval(e, c, L) || c.is_str || c.param >= 0) return false;
+  if (c.is_int && c.v <= INT64_MAX && c.v >= INT64_MIN) m = MVal{true, (int64_t)c.v, 0.0};
+  else m = MVal{false, 0, c.is_int ? (double)c.v : c.dec.to_f64()};
+  return true;
+}
+
 bool const_eval(const Expr &e, CVal &out, Lowering &L) {
+  MathFn mf;
+  if (e.k == EK::FnCall && e.fn() == FnKind::Others && math_fn(e.id.name, mf)) {
+    // a math function of constants folds with the functions the kernels run (its malformed
+    // forms are lower_prog's to report)
+    Lowering quiet;
+    int digits;
+    if (!math_call(e, mf, digits, quiet)) return false;
+    const size_t nv = mf.digits ? 1 : e.kids.size();
+    MVal acc{true, 0, 0.0}, x;
+    for (size_t i = 0; i < nv; ++i) {
+      if (!const_num(e.kids[i], x, L)) return false;
+      if (i == 0 && nv > 1) acc = x;
+      else acc = math_apply(mf.op, mf.digits ? digits : mf.arg, nv > 1 ? acc : x, x);
+    }
+    out = CVal{};
+    if (acc.is_int) {
+      out.v = acc.i;
+      return true;
+    }
+    // (a float constant is an exact decimal: NaN, +-inf and -0.0 stay in the program)
+    if (acc.f - acc.f != 0.0 || (acc.f == 0.0 && jbits(acc.f))) return false;
+    out.is_int = false;
+    out.dec = decimal_of(acc.f);
+    while (out.dec.scale > 0 && !out.dec.digits.empty() && out.dec.digits.back() == '0') out.dec.digits.pop_back(), --out.dec.scale;
+    return true;
+  }
   if (e.k == EK::Literal) {
     const Literal &l = *e.lit;
     if (l.k == LitKind::Integer) {
@@ -947,7 +1060,7 @@ bool lower_prog(nut_plan &p, const Expr &e, PProg &o, Lowering &L) {
         PNode x;
         x.op = op;
         x.arg = arg;
-        if (op >= P_DAYS) x.c.s = expr_text(e);
+        if (op >= P_DAYS || math_op(op)) x.c.s = expr_text(e);
         o.push_back(x);
       };
       if (date_fn(n) >= 0 && na == 1) {
@@ -1043,12 +1156,26 @@ bool lower_prog(nut_plan &p, const Expr &e, PProg &o, Lowering &L) {
         o.push_back(sn);
         return true;
       }
+      MathFn mf;
+      if (math_fn(n, mf)) {
+        // floor / ceil / trunc / round(x[, N]): one node, N its literal; least / greatest of
+        // 2..8 values fold pairwise, left to right
+        int digits;
+        if (!math_call(e, mf, digits, L)) return false;
+        const size_t nv = mf.digits ? 1 : na;
+        for (size_t i = 0; i < nv; ++i) {
+          if (!lower_prog(p, e.kids[i], o, L)) return false;
+          if (i || nv == 1) node(mf.op, mf.digits ? digits : mf.arg);
+        }
+        return true;
+      }
       if (ieq(n, "todate")) return L.fail("toDate takes one 'YYYY-MM-DD' constant or one expression");
       return L.fail("function '" + std::string(n) + "' is not executed (executed: if, multiIf, abs, toFloat64, intDiv, "
                     "modulo, substring, toYear/getYear, toMonth, toDayOfMonth, toQuarter, toDayOfWeek, toDayOfYear, toYYYYMM, "
                     "toYYYYMMDD, toRelativeMonthNum / QuarterNum / WeekNum, toHour, toMinute, toSecond, toDate, toDateTime, "
                     "toStartOfMinute / FiveMinutes / FifteenMinutes / Hour / Day / Week / Month / Quarter / Year, toMonday, "
-                    "toLastDayOfMonth, add / subtract Seconds .. Years, dateDiff)");
+                    "toLastDayOfMonth, add / subtract Seconds .. Years, dateDiff, floor, ceil, trunc, round, sqrt, exp, ln / log, "
+                    "log2, log10, pow, sign, least, greatest, toInt64 / 32 / 16 / 8, toUInt32 / 16 / 8, toFloat32)");
     }
     default: return L.fail("'" + expr_text(e) + "' is not executed (parameters, collections, subqueries)");
   }
@@ -1222,6 +1349,28 @@ bool lower_xpr(nut_plan &p, const Expr &e, XNode &x, Lowering &L) {
     int k = -1;
     if ((ieq(n, "intdiv") || ieq(n, "modulo")) && na == 2) k = ieq(n, "intdiv") ? X_INTDIV : X_MOD;
     if ((ieq(n, "abs") || ieq(n, "tofloat64")) && na == 1) k = ieq(n, "abs") ? X_ABS : X_TOF;
+    MathFn mf;
+    if (math_fn(n, mf)) {  // least / greatest of 2..8 values: nested pairs, left to right
+      int digits;
+      if (!math_call(e, mf, digits, L)) return false;
+      const size_t nv = mf.digits ? 1 : na;
+      XNode acc;
+      for (size_t i = 0; i < nv; ++i) {
+        XNode kid;
+        if (!lower_xpr(p, e.kids[i], kid, L)) return false;
+        if (i == 0 && nv > 1) {
+          acc = std::move(kid);
+          continue;
+        }
+        XNode f;
+        f.k = X_FN, f.op = mf.op, f.arg = mf.digits ? digits : mf.arg;
+        if (nv > 1) f.kids.push_back(std::move(acc));
+        f.kids.push_back(std::move(kid));
+        acc = std::move(f);
+      }
+      x = std::move(acc);
+      return true;
+    }
     if (k >= 0) {
       x.k = k;
       x.kids.resize(na);
@@ -2347,6 +2496,13 @@ std::string prog_text(const nut_plan &p, const PProg &pp) {
     } else if (n.op == NUT_P_NOT || n.op == NUT_P_BITNOT || n.op == NUT_P_ABS || n.op == NUT_P_TO_F64) {
       const char *f = n.op == NUT_P_NOT ? "not" : n.op == NUT_P_BITNOT ? "~" : n.op == NUT_P_ABS ? "abs" : "toFloat64";
       st.push_back(std::string(f) + "(" + pop() + ")");
+    } else if (n.op >= NUT_P_FLOOR && n.op <= NUT_P_ROUND) {
+      st.push_back(math_text(n.op, n.arg) + "(" + pop() + (n.arg ? ", " + std::to_string(n.arg) : std::string()) + ")");
+    } else if (n.op == NUT_P_MATH || n.op == NUT_P_SIGN || n.op == NUT_P_CAST) {
+      st.push_back(math_text(n.op, n.arg) + "(" + pop() + ")");
+    } else if (n.op == NUT_P_POW || n.op == NUT_P_LEAST || n.op == NUT_P_GREATEST) {
+      std::string r = pop(), l = pop();
+      st.push_back(math_text(n.op, n.arg) + "(" + l + ", " + r + ")");
     } else if (n.op == NUT_P_IF) {
       std::string e = pop(), t = pop(), c = pop();
       st.push_back("if(" + c + ", " + t + ", " + e + ")");

@@ -10,25 +10,6 @@ int table_kind_flag(const TCol &c) {
   return c.kind == NUT_COL_DATE ? NUT_COL_AS_DATE : c.kind == NUT_COL_DATETIME ? NUT_COL_AS_DATETIME : 0;
 }
 
-// exact decimal of a finite double (17 significant digits: strtod gives the double back)
-Decimal decimal_of(double d) {
-  Decimal x;
-  if (d == 0.0) return x;
-  char buf[64];
-  snprintf(buf, sizeof buf, "%.16e", d);  // [-]d.dddddddddddddddde[+-]XX
-  const char *q = buf;
-  if (*q == '-') x.neg = true, ++q;
-  std::string digs;
-  for (; *q && *q != 'e'; ++q)
-    if (*q != '.') digs += *q;
-  const int64_t ex = strtoll(q + 1, nullptr, 10);
-  size_t z = 0;
-  while (z < digs.size() && digs[z] == '0') ++z;
-  x.digits = digs.substr(z);
-  x.scale = 16 - ex;
-  return x;
-}
-
 // Scalar subqueries (nut_plan.subs): run each (run(sub) executes it over the caller's
 // binding), check it returned one value, and copy the plan with every placeholder constant
 // replaced by that value.  A global aggregate over no rows is one row of defaults

@@ -80,10 +80,12 @@ struct PlanAgg {
 // Arithmetic over a group's outputs (SELECT sum(a) / count(), 100 * sum(x) / sum(y), ...),
 // evaluated on the host per result group with nut_prog semantics: int + - * wrap, an f64
 // operand makes the op f64, / is always f64, % and intDiv truncate (a zero divisor fails).
-enum XKind { X_CONST, X_OUT, X_ADD, X_SUB, X_MUL, X_DIV, X_MOD, X_INTDIV, X_ABS, X_TOF };
+// X_FN: a math op (NUT_P_FLOOR .. NUT_P_CAST) of one or two operands, with the node's literal
+enum XKind { X_CONST, X_OUT, X_ADD, X_SUB, X_MUL, X_DIV, X_MOD, X_INTDIV, X_ABS, X_TOF, X_FN };
 struct XNode {
   int k = X_CONST;
   int out = -1;  // X_OUT: output index (a key, an aggregate or avg)
+  int op = 0, arg = 0;  // X_FN: nut_prog_op and its node's arg
   bool is_int = true;
   int64_t i = 0;
   double f = 0;
@@ -108,6 +110,61 @@ struct HNode {
   int param = -1;    // H_CONST: >= 0, the value of scalar subquery nut_plan.subs[param]
   std::vector<HNode> kids;
 };
+
+// The math ops (NUT_P_FLOOR .. NUT_P_CAST) on the host: constant folding and arithmetic over
+// group outputs.  The exactly defined ones are prog_ops.hpp's functions; exp, ln, log2, log10
+// and pow are libm's under the device's NaN rule (include/nutexec.h).
+struct MVal {
+  bool is_int;
+  int64_t i;
+  double f;
+  double as_f() const { return is_int ? (double)i : f; }
+};
+inline double host_nan(double r, double a, double b) {
+  if (r == r) return r;
+  return a != a ? jquiet(a) : b != b ? jquiet(b) : jnegnan();
+}
+inline bool math_op(int op) { return op >= NUT_P_FLOOR && op <= NUT_P_CAST; }
+// true if the op's result is an integer for operands of these types
+inline bool math_is_int(int op, int arg, bool a_int, bool b_int) {
+  if (op >= NUT_P_FLOOR && op <= NUT_P_ROUND) return a_int;
+  if (op == NUT_P_SIGN) return true;
+  if (op == NUT_P_LEAST || op == NUT_P_GREATEST) return a_int && b_int;
+  if (op == NUT_P_CAST) return arg != NUT_CAST_F32;
+  return false;
+}
+inline MVal math_apply(int op, int arg, const MVal &a, const MVal &b) {
+  const double x = a.as_f(), y = b.as_f();
+  switch (op) {
+    case NUT_P_FLOOR:
+    case NUT_P_CEIL:
+    case NUT_P_TRUNC:
+    case NUT_P_ROUND:
+      return a.is_int ? MVal{true, jroundi(a.i, op - NUT_P_FLOOR, arg), 0.0} : MVal{false, 0, jroundf(a.f, op - NUT_P_FLOOR, arg)};
+    case NUT_P_MATH:
+      return MVal{false, 0,
+                  arg == NUT_MF_SQRT ? jsqrt(x)
+                                     : host_nan(arg == NUT_MF_EXP ? exp(x) : arg == NUT_MF_LN ? log(x)
+                                                : arg == NUT_MF_LOG2 ? log2(x) : log10(x), x, x)};
+    case NUT_P_POW: return MVal{false, 0, host_nan(pow(x, y), x, y)};
+    case NUT_P_SIGN: return MVal{true, a.is_int ? jsigni(a.i) : jsignf(a.f), 0.0};
+    case NUT_P_LEAST:
+      return a.is_int && b.is_int ? MVal{true, jleasti(a.i, b.i), 0.0} : MVal{false, 0, jleastf(x, y)};
+    case NUT_P_GREATEST:
+      return a.is_int && b.is_int ? MVal{true, jgreatesti(a.i, b.i), 0.0} : MVal{false, 0, jgreatestf(x, y)};
+    default:  // NUT_P_CAST
+      if (arg == NUT_CAST_F32) return MVal{false, 0, a.is_int ? jtof32i(a.i) : jtof32(a.f)};
+      return MVal{true, jnarrow(a.is_int ? a.i : jtoi64(a.f), arg), 0.0};
+  }
+}
+// SQL names of the math ops: op / arg of the node, argument counts, and whether a second
+// argument is the constant digit count
+struct MathFn {
+  int op = 0, arg = 0, lo = 1, hi = 1;
+  bool digits = false;
+};
+bool math_fn(sv n, MathFn &f);
+std::string math_text(int op, int arg);
 
 extern const char *kCmpText[];
 }  // namespace plan
@@ -332,6 +389,7 @@ bool ieq(sv a, sv b);
 std::string i128_str(i128 v);
 void json_str(std::string &o, sv s);
 i128 sat_from_u128(u128 m, bool neg);
+Decimal decimal_of(double d);
 // literal dates and `date +/- interval n month` over constants (any year, any month count);
 // the program ops fold with their own functions (prog_ops.hpp)
 int64_t days_from_civil(int64_t y, unsigned m, unsigned d);
