@@ -556,6 +556,43 @@ nut_status nut_join_i64_into(nut_ctx *ctx, const int64_t *build, uint64_t nbuild
  * keys with chosen home slots from it. */
 nut_status nut_join_layout(uint64_t nbuild, int64_t key, int region_built, uint64_t *capacity, uint64_t *home,
                            uint64_t *wrap_block, uint64_t *region_slots, uint64_t *region_limit);
+/* The layout of the group-by's tables and of its streaming launch (host only: no context,
+ * no device, nothing runs; csrc/gb_layout.hpp is the one definition the kernels use too).
+ * A test hook: tests compute keys with chosen buckets, slots, shards and digits from it
+ * (DESIGN.md §4.2e). */
+typedef struct nut_groupby_layout_query {
+  int32_t nkeys, naggs;     /* 1 or 2 keys; 0..NUT_MAX_AGGS aggregates */
+  uint64_t group_hint;      /* as passed to the launch (nut_groupby's group_hint; accumulate: its rows) */
+  int32_t segment;          /* 1: segment mode (a partition per workgroup), 0: streaming */
+  int32_t slots_per_group;  /* NUT_OPT_AGG_SLOTS (segment: NUT_OPT_GB_SEG_SLOTS); 0: the option's default */
+  uint64_t table_cap;       /* slots of the global table, a power of two >= 1024; 0: the first table of this hint */
+  int32_t num_cus;          /* compute units of the device (nut_ctx_info) */
+  int32_t agg_blocks;       /* NUT_OPT_AGG_BLOCKS */
+  int32_t expr_kernel;      /* 1: a run-time compiled (expression mode) kernel, 0: a compiled one other than Q1's */
+  uint64_t n;               /* rows of the launch */
+  int64_t key[2];           /* the key tuple (key[1] ignored for one key) */
+} nut_groupby_layout_query;
+typedef struct nut_groupby_layout_info {
+  /* on-chip table of a workgroup: slots (0: none), claims admitted, private groups per thread (0: shared table) */
+  uint32_t lds_cap, lds_limit, priv;
+  /* the tuple there: slot word, first slot of its home bucket (of lds_bucket slots), direct-map index
+   * (direct_size: outside the map) */
+  uint32_t lds_home, lds_bucket, direct_idx, direct_size;
+  uint64_t lds_word;
+  /* global table: slots, the tuple's hash, home slot and tag, its claim shard and arena shard */
+  uint64_t table_cap, hash, home;
+  uint32_t tag, claim_shard, arena_shard;
+  /* claims before overflow is flagged, shards, claims and arena entries per shard, arena entries */
+  uint32_t limit, nshards, limit_shard, arena_shard_limit, arena_cap;
+  /* the launch: threads per workgroup, workgroups per CU, workgroups */
+  uint32_t threads, blocks_per_cu;
+  uint64_t blocks;
+  /* partitioned group-by from this hint (default options): levels, level 0's digit bits, the tuple's digit,
+   * and its 64-bit owner hash (nut_groups_partition: part = owner_hash mod nparts) */
+  uint32_t levels, l0_bits, l0_digit;
+  uint64_t owner_hash;
+} nut_groupby_layout_info;
+nut_status nut_groupby_layout(const nut_groupby_layout_query *q, nut_groupby_layout_info *out);
 /* Expression-mode scan + compaction: the row ids (ascending) of the
  * rows where s->where holds — any program over s->prog_col, compiled for the query like
  * the expression-mode group-by.  Reads s->n, s->where and the program columns only (keys

@@ -115,6 +115,26 @@ class NutColumn(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("type", C.c_int32)]
 
 
+class NutGroupbyLayoutQuery(C.Structure):
+    """nut_groupby_layout_query"""
+    _fields_ = [("nkeys", C.c_int32), ("naggs", C.c_int32), ("group_hint", C.c_uint64), ("segment", C.c_int32),
+                ("slots_per_group", C.c_int32), ("table_cap", C.c_uint64), ("num_cus", C.c_int32),
+                ("agg_blocks", C.c_int32), ("expr_kernel", C.c_int32), ("n", C.c_uint64), ("key", C.c_int64 * 2)]
+
+
+class NutGroupbyLayoutInfo(C.Structure):
+    """nut_groupby_layout_info"""
+    _fields_ = [("lds_cap", C.c_uint32), ("lds_limit", C.c_uint32), ("priv", C.c_uint32),
+                ("lds_home", C.c_uint32), ("lds_bucket", C.c_uint32), ("direct_idx", C.c_uint32),
+                ("direct_size", C.c_uint32), ("lds_word", C.c_uint64),
+                ("table_cap", C.c_uint64), ("hash", C.c_uint64), ("home", C.c_uint64),
+                ("tag", C.c_uint32), ("claim_shard", C.c_uint32), ("arena_shard", C.c_uint32),
+                ("limit", C.c_uint32), ("nshards", C.c_uint32), ("limit_shard", C.c_uint32),
+                ("arena_shard_limit", C.c_uint32), ("arena_cap", C.c_uint32),
+                ("threads", C.c_uint32), ("blocks_per_cu", C.c_uint32), ("blocks", C.c_uint64),
+                ("levels", C.c_uint32), ("l0_bits", C.c_uint32), ("l0_digit", C.c_uint32), ("owner_hash", C.c_uint64)]
+
+
 PLAN_FILTER, PLAN_GROUPBY, PLAN_SORT = 0, 1, 2
 STMT_KINDS = ["Select", "Insert", "Explain", "Alter", "Create", "Describe", "Drop", "Truncate", "Optimize", "Set"]
 # TokenType order (reference src/parser/tokenizer/token.rs:5-91)
@@ -175,6 +195,7 @@ SIGNATURES = {
     "nut_filter_i64_async": (_I32, [_P, _P, _U64, _I32, _I64, _P, _P]),
     "nut_groupby": (_I32, [_P, C.POINTER(NutAggSpec), _U64, C.POINTER(_P)]),
     "nut_groupby_accumulate": (_I32, [_P, C.POINTER(NutAggSpec), _P]),
+    "nut_groupby_layout": (_I32, [C.POINTER(NutGroupbyLayoutQuery), C.POINTER(NutGroupbyLayoutInfo)]),
     "nut_prog_type": (_I32, [C.POINTER(NutProg), C.POINTER(C.c_int32), _I32, C.POINTER(C.c_int32)]),
     "nut_groupby_jit_source": (_I32, [C.POINTER(NutAggSpec), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nut_groupby_jit_compile": (_I32, [C.POINTER(NutAggSpec)]),

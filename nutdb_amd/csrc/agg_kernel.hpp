@@ -23,12 +23,9 @@
 namespace nut {
 
 // ------------------------------------------------------------------ LDS table
-// Layout (dynamic LDS, this order, 16-B aligned):
-//   slot[cap+1] u64 | agg[na][cap+1] u64 | k12[cap+1] {i64,i64} (NK=2) | did[cap+1] u32
-//   (PRIV) | dslot[kPrivMax] u32 + dmap[kDirect] u32 (PRIV) | ctl[4] u32 | priv[P][na][BD] u64 (PRIV)
+// (layout of the dynamic LDS, slot words, home buckets and the direct map: gb_layout.hpp)
 enum { CTL_CLAIMED = 0, CTL_SPECIAL = 1, CTL_LOCK = 2, CTL_NDENSE = 3 };
 constexpr uint32_t kNoDense = 0xFFFFFFFFu;
-constexpr uint32_t kDirect = 256;  // direct-map entries (PRIV): key < 256, or 16 x 16 key pairs
 
 struct LTable {
   uint64_t *slot, *agg;
@@ -39,51 +36,6 @@ struct LTable {
   uint32_t *spill;  // spill mode: the block's append cursor (LDS)
   uint32_t *shist;  //   and its histogram of the key hash's top byte (LDS, 256)
 };
-
-__host__ __device__ inline size_t lds_layout(uint32_t cap, int nk, int na, bool privm, int P, int bd,
-                                             size_t *o_k12, size_t *o_did, size_t *o_dslot, size_t *o_ctl,
-                                             size_t *o_priv) {
-  const size_t stride = cap + 1;
-  size_t o = stride * 8 * (1 + (size_t)na);
-  o = (o + 15) & ~size_t(15);
-  *o_k12 = o;
-  if (nk == 2) o += stride * 16;
-  *o_did = o;
-  if (privm) o += stride * 4;
-  *o_dslot = o;
-  if (privm) o += (kPrivMax + kDirect) * 4;
-  *o_ctl = o;
-  o += 16;
-  o = (o + 15) & ~size_t(15);
-  *o_priv = o;
-  if (privm) o += (size_t)P * na * bd * 8;
-  return (o + 15) & ~size_t(15);
-}
-
-// slot word of a key: the key itself (one key) or a 64-bit hash nudged off the empty
-// marker (two keys; the tuple is verified against k12)
-template <int NK>
-__device__ __forceinline__ uint64_t lkey(uint64_t k1, uint64_t k2) {
-  if (NK == 1) return k1;
-  uint64_t h = k1 * kGolden ^ ((k2 + 0x632BE59BD9B4E019ull) * 0xC2B2AE3D27D4EB4Full);
-  h ^= h >> 29;
-  return h == kEmpty ? h ^ 1ull : h;
-}
-// home bucket (4 slots, 32-B aligned) of a slot word
-constexpr uint32_t kBucket = 4;
-// on-chip table home: Fibonacci hash of the xor-folded key (3 VALU ops; the table has
-// at most 2^15 slots, so 32 product bits are plenty)
-__device__ __forceinline__ uint32_t lhome(uint64_t w, int log2cap) {
-  const uint32_t f = (uint32_t)w ^ (uint32_t)(w >> 32);
-  return ((f * 0x9E3779B1u) >> (32 - log2cap)) & ~(kBucket - 1);
-}
-
-// direct-map index of a key (tuple), or kDirect when it is out of the map's range
-template <int NK>
-__device__ __forceinline__ uint32_t direct_idx(uint64_t k1, uint64_t k2) {
-  if (NK == 1) return k1 < kDirect ? (uint32_t)k1 : kDirect;
-  return (k1 | k2) < 16 ? (uint32_t)(k1 << 4 | k2) : kDirect;
-}
 
 template <int NK>
 __device__ __forceinline__ bool keys_match(const LTable &t, uint32_t s, uint64_t k1, uint64_t k2) {

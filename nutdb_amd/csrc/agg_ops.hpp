@@ -22,7 +22,6 @@
 
 namespace nut {
 
-constexpr int kPrivMax = 8;  // private groups per thread (upper bound)
 constexpr int kMaxCols = NUT_MAX_PROG_COLS;  // value columns a kernel can load
 constexpr int kMaxConst = 64;                // expression constants (kernel arguments)
 

@@ -151,15 +151,13 @@ int32_t kind_of(const nut_agg_spec *s, int a) {
   }
 }
 
-// LDS bytes of a table with `cap` slots (+1 special); two-key tables add a key arena
-// of `cap` tuples (3/4 of it holds admitted keys, the rest absorbs lost claim races)
-// (re)allocate the global table for `cap` slots and initialise it on the stream
+// (re)allocate the global table for `cap` slots and initialise it on the stream; its limits,
+// shards and two-key arena follow gb_table_rule (gb_layout.hpp)
 nut_status alloc_table(nut_groups *g, uint64_t cap) {
   g->ctl_valid = false;
   const uint64_t stride = cap + 1;
-  // two-key arena: one entry per claimable slot plus slack for claim races lost by
-  // concurrent inserters of the same key (each loser leaks at most one entry)
-  const uint64_t arena = g->nk == 2 ? cap + 65536 : 0;
+  const GbTableRule rule = gb_table_rule(cap, g->nk);
+  const uint64_t arena = rule.arena;
   size_t off = 0;
   auto carve = [&](size_t bytes) {
     size_t o = off;
@@ -171,7 +169,7 @@ nut_status alloc_table(nut_groups *g, uint64_t cap) {
   size_t o_a1 = carve(arena * 8 + 8);
   size_t o_a2 = carve(arena * 8 + 8);
   size_t o_ctl = carve(64);
-  const int nsh_log2 = cap >= (1ull << 18) ? 8 : 0;
+  const int nsh_log2 = rule.nsh_log2;
   const uint32_t nsh = 1u << nsh_log2;
   size_t o_sh = carve((size_t)nsh * 2 * 16 * 4);
   size_t o_gt = carve(sizeof(GTable));
@@ -194,11 +192,10 @@ nut_status alloc_table(nut_groups *g, uint64_t cap) {
   t.nsh_log2 = nsh_log2;
   t.cap = cap;
   t.log2cap = ilog2(cap);
-  t.limit = (uint32_t)std::min<uint64_t>(cap - cap / 4, 0xFFFFFFF0ull);
-  t.arena_cap = (uint32_t)std::min<uint64_t>(arena, 0xFFFFFFF0ull);
-  // per shard: the claims of a uniformly hashed 1/nsh of the slots, +1/16 for variance
-  t.limit_sh = nsh == 1 ? t.limit : t.limit / nsh + t.limit / nsh / 16;
-  t.arena_sh = t.arena_cap / nsh;
+  t.limit = rule.limit;
+  t.arena_cap = rule.arena_cap;
+  t.limit_sh = rule.limit_sh;
+  t.arena_sh = rule.arena_sh;
   t.naggs = g->naggs;
   t.kinds = pack_kinds(g->kinds, g->naggs);
   g->dev_gt = (GTable *)(b + o_gt);
@@ -264,9 +261,6 @@ int detect_shape(const nut_agg_spec *s, const int32_t *kinds, const AggArgs &a) 
   return SHAPE_GENERIC;
 }
 
-constexpr int kBdShared = 512;
-constexpr int kBdPriv = 256;
-
 // Compiled shapes assume 16-B aligned columns (vector loads); anything else runs the
 // generic kernel, which decides the load width at run time.
 KernelFn pick_kernel(int nk, bool priv, int shape, bool vec, int bd) {
@@ -284,12 +278,6 @@ KernelFn pick_kernel(int nk, bool priv, int shape, bool vec, int bd) {
   if (shape == SHAPE_SUMCOUNT) return agg_kernel<1, false, kBdShared, ShapeSumCount, 1>;
   if (shape == SHAPE_ALL4) return agg_kernel<1, false, kBdShared, ShapeAll4, 1>;
   return nk == 1 ? agg_kernel<1, false, kBdShared, Generic, 0> : agg_kernel<2, false, kBdShared, Generic, 0>;
-}
-
-size_t lds_bytes(uint32_t cap, int nk, int na, bool priv, int P, int bd) {
-  if (cap == 0) return 0;
-  size_t a, b, c, d, e;
-  return lds_layout(cap, nk, na, priv, P, bd, &a, &b, &c, &d, &e);
 }
 
 // Partitioned aggregation (gpart.hpp) drives the same kernels in two extra modes.
@@ -329,17 +317,10 @@ static PrivShape priv_shape_of(int dev) {
   return dev >= 0 && dev < 64 ? g_priv_shape[dev] : PrivShape{};
 }
 
-// the on-chip table of a launch: 4x the expected groups (load <= 1/4: a key almost always
-// sits in its 4-slot home bucket) within the LDS budget; segment mode: NUT_OPT_GB_SEG_SLOTS x
-// group_hint (already twice a partition's expected groups).  0: hot keys cannot fit on chip
-constexpr size_t kAggLdsMax = 160 * 1024 - 2048;  // the kernel also holds static LDS (spill cursor, histogram)
+// the on-chip table of a launch (gb_lds_cap): NUT_OPT_AGG_SLOTS x the expected groups;
+// segment mode: NUT_OPT_GB_SEG_SLOTS x group_hint (already twice a partition's expected groups)
 uint32_t agg_lcap(nut_ctx *c, int nk, int na, uint64_t group_hint, bool seg) {
-  // (32 slots = 8 buckets x 32 B = one pass over the 64 LDS banks: for <= 8 groups two
-  // home buckets never conflict — distinct buckets hit distinct banks, equal ones broadcast)
-  const uint64_t want = group_hint ? (uint64_t)c->opt[seg ? NUT_OPT_GB_SEG_SLOTS : NUT_OPT_AGG_SLOTS] * group_hint : 4096;
-  uint32_t lcap = 32;
-  while (lcap < want && lds_bytes(lcap * 2, nk, na, false, 0, kBdShared) <= kAggLdsMax) lcap *= 2;
-  return group_hint > 8ull * lcap ? 0 : lcap;
+  return gb_lds_cap(nk, na, group_hint, (uint64_t)c->opt[seg ? NUT_OPT_GB_SEG_SLOTS : NUT_OPT_AGG_SLOTS]);
 }
 
 // launch the streaming aggregation of spec's rows into g's table.  `kinds` are the
@@ -409,11 +390,7 @@ nut_status launch_agg(nut_groups *g, const nut_agg_spec *s, uint64_t group_hint,
     for (int i = 0; i < NUT_MAX_AGGS; ++i) a.sp_map[i] = ex->sp_map[i];
   }
   // private accumulators when every expected group fits P per thread, 2 blocks per CU
-  int P = 0;
-  if (lcap && group_hint && group_hint <= (uint64_t)kPrivMax && na > 0 && !(ex && ex->seg_off)) {
-    P = (int)group_hint;
-    if (lds_bytes(lcap, g->nk, na, true, P, kBdPriv) > lds_max / 2) P = 0;
-  }
+  const int P = gb_priv_groups(lcap, g->nk, na, group_hint, ex && ex->seg_off);
   const bool priv = P > 0;
   const int shape = detect_shape(s, kinds, a);
   // private-accumulator kernels built for 128 / 192 / 256 threads: the compiled Q1 shape
@@ -424,7 +401,7 @@ nut_status launch_agg(nut_groups *g, const nut_agg_spec *s, uint64_t group_hint,
   // fold's latency exposed (8.7 ms) — NUT_OPT_PRIV_BD / _BLOCKS override for sweeps.  The
   // compiled (fused) Q1 kernel takes the shape its device's probe chose (kPrivShapes).
   const bool q1_fused = q1_tuned && !s->prog_mode;
-  int pbd = 192, pblocks = 2;
+  int pbd = kBdPrivTuned, pblocks = kPrivTunedBlocks;
   if (q1_fused) {
     const int k = c->priv_probe >= 0 ? c->priv_probe : priv_shape_of(c->device).shape;
     if (k >= 0) pbd = kPrivShapes[k][0], pblocks = kPrivShapes[k][1];
@@ -433,21 +410,19 @@ nut_status launch_agg(nut_groups *g, const nut_agg_spec *s, uint64_t group_hint,
     ex->q1_fused = q1_fused;
     return NUT_OK;
   }
-  const int bd = !priv ? kBdShared : !q1_tuned ? kBdPriv : c->opt[NUT_OPT_PRIV_BD] ? (int)c->opt[NUT_OPT_PRIV_BD] : pbd;
+  const int bd = gb_threads(priv, q1_tuned, c->opt[NUT_OPT_PRIV_BD] ? (int)c->opt[NUT_OPT_PRIV_BD] : pbd);
   a.lds_cap = lcap;
-  a.lds_limit = lcap - lcap / 4;
+  a.lds_limit = gb_lds_limit(lcap);
   a.lds_log2 = lcap ? ilog2(lcap) : 0;
   a.priv = P;
   a.gt = g->dev_gt;
   const size_t lb = lds_bytes(lcap, g->nk, na, priv, P, bd);
-  int blocks_per_cu = lb ? (int)std::max<size_t>(1, std::min<size_t>(bd == 512 ? 4 : 8, lds_max / lb)) : 4;
-  if (q1_tuned)
-    blocks_per_cu = std::min<int>(blocks_per_cu, c->opt[NUT_OPT_PRIV_BLOCKS] ? (int)c->opt[NUT_OPT_PRIV_BLOCKS]
-                                                 : q1_fused ? pblocks : 2);
-  if (!priv && c->opt[NUT_OPT_AGG_BLOCKS]) blocks_per_cu = std::min<int>(blocks_per_cu, (int)c->opt[NUT_OPT_AGG_BLOCKS]);
+  const int blocks_per_cu =
+      gb_blocks_per_cu(lb, bd, priv, q1_tuned,
+                       c->opt[NUT_OPT_PRIV_BLOCKS] ? (int)c->opt[NUT_OPT_PRIV_BLOCKS] : q1_fused ? pblocks : kPrivTunedBlocks,
+                       (int)c->opt[NUT_OPT_AGG_BLOCKS]);
   uint64_t pairs = (s->n + 1) / 2;
-  uint64_t blocks = std::min<uint64_t>((uint64_t)c->num_cus * blocks_per_cu, (pairs + bd - 1) / bd);
-  if (blocks == 0) blocks = 1;
+  uint64_t blocks = gb_grid(c->num_cus, blocks_per_cu, s->n, bd);
   if (ex && ex->seg_off) {  // one block per segment (segments start at even rows)
     a.seg_off = ex->seg_off;
     a.seg_end = ex->seg_end;
@@ -494,12 +469,6 @@ nut_status launch_agg(nut_groups *g, const nut_agg_spec *s, uint64_t group_hint,
   c->timer.end(c->stream);
   NUT_HIP(hipGetLastError());
   return NUT_OK;
-}
-
-uint64_t table_cap_for(uint64_t groups) {
-  uint64_t cap = 1024;
-  while (cap < 2 * groups) cap *= 2;
-  return cap;
 }
 
 // grow the table (rehash existing groups) so that `extra` more groups fit
@@ -824,7 +793,7 @@ nut_status groupby_partitioned_direct(nut_groups *g, const nut_agg_spec *s, uint
   const int narr = 3 + nv;
   const uint64_t rows = (n + 2 * 65536 + 64 + 31) & ~31ull;  // + one alignment gap per partition
   const int nstore = narr - 1 - (nk == 1 ? 1 : 0);
-  const int levels = c->opt[NUT_OPT_GB_LEVELS] ? (int)c->opt[NUT_OPT_GB_LEVELS] : group_hint > 256ull * 1024 ? 2 : 1;
+  const int levels = gb_levels(group_hint, (int)c->opt[NUT_OPT_GB_LEVELS]);
   const bool opt = c->opt[NUT_OPT_GB_OPTIMISTIC] != 0;
   c->gb_path = NUT_GB_PARTITIONED_DIRECT;
   c->gb_levels = (uint32_t)levels;
@@ -838,8 +807,7 @@ nut_status groupby_partitioned_direct(nut_groups *g, const nut_agg_spec *s, uint
   // level 0's digit: 7 bits for one level up to 150 K groups (128 partitions of <= ~1200
   // groups still fit a workgroup's 2048-slot table; the runs are twice as long: G = 1e5
   // 9.98 vs 10.56 ms kernels, same box), else 8 (two levels: G = 1e7 18.4 vs 18.6 ms)
-  const int bits0 = c->opt[NUT_OPT_GB_L0_BITS] >= 6 ? (int)c->opt[NUT_OPT_GB_L0_BITS]
-                    : levels == 1 && group_hint <= 150000 ? 7 : 8;
+  const int bits0 = gb_l0_bits(levels, group_hint, (int)c->opt[NUT_OPT_GB_L0_BITS]);
   const int bits1 = (int)c->opt[NUT_OPT_GB_L1_BITS];
   const double lam = (double)group_hint / ((double)(1 << bits0) * (1 << bits1));
   const double slack1 = levels == 2 && opt && lam >= 100 ? 1.0 + 6.0 / sqrt(lam) : 0.0;
@@ -1752,7 +1720,7 @@ nut_status groupby_partitioned(nut_groups *g, const nut_agg_spec *s, uint64_t gr
   }
   if (nsp == 0) return NUT_OK;
   // ---- 2. partition by the key hash: 256 or 65536 partitions of ~<= 1K groups
-  const int levels = c->opt[NUT_OPT_GB_LEVELS] ? (int)c->opt[NUT_OPT_GB_LEVELS] : group_hint > 256ull * 1024 ? 2 : 1;
+  const int levels = gb_levels(group_hint, (int)c->opt[NUT_OPT_GB_LEVELS]);
   c->gb_path = NUT_GB_PARTITIONED_SPILL;
   c->gb_levels = (uint32_t)levels;
   c->gb_optimistic = 0;
@@ -1975,6 +1943,53 @@ nut_status nut_groupby_accumulate(nut_ctx *c, const nut_agg_spec *s, nut_groups 
   if (st) return st;
   if (ctl[1] & 2u) return fail(NUT_ERR_INVALID_ARG, "nut_groupby_accumulate: division by zero in an expression");
   if (ctl[1]) return fail(NUT_ERR_OOM, "nut_groupby_accumulate: table overflow");
+  return NUT_OK;
+}
+
+// host only: what agg_lcap / launch_agg / alloc_table decide for this query with the default
+// options, and the tuple's place in the tables (gb_layout.hpp)
+nut_status nut_groupby_layout(const nut_groupby_layout_query *q, nut_groupby_layout_info *o) {
+  if (!q || !o) return fail(NUT_ERR_INVALID_ARG, "nut_groupby_layout: NULL argument");
+  if (q->nkeys < 1 || q->nkeys > 2 || q->naggs < 0 || q->naggs > NUT_MAX_AGGS || q->num_cus < 1 ||
+      q->slots_per_group < 0 || q->slots_per_group > 8 || q->agg_blocks < 0)
+    return fail(NUT_ERR_INVALID_ARG, "nut_groupby_layout: bad argument");
+  if (q->table_cap && (q->table_cap < 1024 || (q->table_cap & (q->table_cap - 1)) || q->table_cap > (1ull << 34)))
+    return fail(NUT_ERR_INVALID_ARG, "nut_groupby_layout: table_cap is no power of two in [2^10, 2^34]");
+  memset(o, 0, sizeof(*o));
+  nut_ctx def;  // the default options
+  if (q->slots_per_group) def.opt[q->segment ? NUT_OPT_GB_SEG_SLOTS : NUT_OPT_AGG_SLOTS] = q->slots_per_group;
+  const int nk = q->nkeys, na = q->naggs;
+  const uint64_t k1 = (uint64_t)q->key[0], k2 = nk == 2 ? (uint64_t)q->key[1] : 0;
+  o->lds_cap = agg_lcap(&def, nk, na, q->group_hint, q->segment != 0);
+  o->lds_limit = gb_lds_limit(o->lds_cap);
+  o->priv = (uint32_t)gb_priv_groups(o->lds_cap, nk, na, q->group_hint, q->segment != 0);
+  o->lds_word = nk == 1 ? lkey<1>(k1, k2) : lkey<2>(k1, k2);
+  o->lds_home = o->lds_cap ? lhome(o->lds_word, ilog2(o->lds_cap)) : 0;
+  o->lds_bucket = kBucket;
+  o->direct_idx = nk == 1 ? direct_idx<1>(k1, k2) : direct_idx<2>(k1, k2);
+  o->direct_size = kDirect;
+  o->table_cap = q->table_cap ? q->table_cap : table_cap_for(q->group_hint ? q->group_hint : 8192);
+  const GbTableRule rule = gb_table_rule(o->table_cap, nk);
+  o->hash = nk == 1 ? key_hash<1>((int64_t)k1, 0) : key_hash<2>((int64_t)k1, (int64_t)k2);
+  o->home = slot_of(o->hash, ilog2(o->table_cap));
+  o->tag = (uint32_t)(o->hash >> 32);
+  o->claim_shard = (uint32_t)gb_claim_shard(o->home, rule.nsh_log2);
+  o->arena_shard = gb_arena_shard(o->tag, rule.nsh_log2);
+  o->limit = rule.limit;
+  o->nshards = 1u << rule.nsh_log2;
+  o->limit_shard = rule.limit_sh;
+  o->arena_shard_limit = rule.arena_sh;
+  o->arena_cap = rule.arena_cap;
+  const bool priv = o->priv > 0, tuned = priv && q->expr_kernel;
+  const int bd = gb_threads(priv, tuned, kBdPrivTuned);
+  const size_t lb = lds_bytes(o->lds_cap, nk, na, priv, (int)o->priv, bd);
+  o->threads = (uint32_t)bd;
+  o->blocks_per_cu = (uint32_t)gb_blocks_per_cu(lb, bd, priv, tuned, kPrivTunedBlocks, q->agg_blocks);
+  o->blocks = gb_grid(q->num_cus, (int)o->blocks_per_cu, q->n, bd);
+  o->levels = (uint32_t)gb_levels(q->group_hint, (int)def.opt[NUT_OPT_GB_LEVELS]);
+  o->l0_bits = (uint32_t)gb_l0_bits((int)o->levels, q->group_hint, (int)def.opt[NUT_OPT_GB_L0_BITS]);
+  o->l0_digit = gb_digit(k1, k2, nk, 64 - (int)o->l0_bits, 0);
+  o->owner_hash = owner_hash(k1, k2, nk);
   return NUT_OK;
 }
 

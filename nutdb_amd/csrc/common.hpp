@@ -40,10 +40,6 @@ __device__ __forceinline__ uint64_t fp2(uint64_t k1, uint64_t k2) {
   uint64_t f = mix64(k1 ^ mix64(k2 + kGolden));
   return f == kEmpty ? (kEmpty ^ 1ull) : f;
 }
-// multiply-shift slot index
-__device__ __forceinline__ uint32_t slot_of(uint64_t fp, int log2cap) {
-  return (uint32_t)((fp * kGolden) >> (64 - log2cap));
-}
 
 // IEEE total order on f64 bit patterns, mapped to an unsigned integer order
 __host__ __device__ __forceinline__ uint64_t f64_to_ord(uint64_t b) {

@@ -64,7 +64,7 @@ struct GpRange {
 // owner_hash(k ^ kx) with its own kx, independent of the multi-GPU owner (kx = 0)
 __device__ __forceinline__ uint32_t gp_digit(const uint64_t *k1, const uint64_t *k2, uint64_t i, int shift,
                                              uint64_t kx) {
-  return (uint32_t)(owner_hash(k1[i] ^ kx, k2 ? k2[i] : 0, k2 ? 2 : 1) >> shift) & 255u;
+  return gb_digit(k1[i], k2 ? k2[i] : 0, k2 ? 2 : 1, shift, kx);
 }
 
 // 256-bin histogram of (hash >> shift) & 255 per segment (gather: one for all segments)

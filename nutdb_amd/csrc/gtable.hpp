@@ -12,6 +12,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "gb_layout.hpp"
 
 namespace nut {
 
@@ -84,12 +85,7 @@ __device__ __forceinline__ void agg_merge_word(uint64_t *w, int kind, uint64_t x
   }
 }
 
-// hash of the key tuple: single key -> the key itself is the slot word; two keys ->
-// 64-bit mix (tag = high half, slot from multiply-shift)
-template <int NK>
-__device__ __forceinline__ uint64_t key_hash(int64_t k1, int64_t k2) {
-  return NK == 1 ? (uint64_t)k1 : mix64((uint64_t)k1 ^ mix64((uint64_t)k2 + kGolden));
-}
+// (key_hash, slot_of and the shard of a claim or an arena entry: gb_layout.hpp)
 
 // ---- global table: find or claim the slot of a key tuple; -1 on overflow
 template <int NK>
@@ -114,7 +110,7 @@ __device__ __forceinline__ int64_t g_find(const GTable &t, uint64_t h, int64_t k
       uint64_t old = atomicCAS((unsigned long long *)&t.slot[s], (unsigned long long)kEmpty,
                                (unsigned long long)h);
       if (old == kEmpty) {
-        if (atomicAdd(&t.shard[(s & ((1u << t.nsh_log2) - 1)) * 16], 1u) >= t.limit_sh) atomicOr(&t.ctl[1], 1u);
+        if (atomicAdd(&t.shard[(s & (gb_shards(t.nsh_log2) - 1)) * 16], 1u) >= t.limit_sh) atomicOr(&t.ctl[1], 1u);
         return (int64_t)s;
       }
       if (old == h) return (int64_t)s;
@@ -122,8 +118,8 @@ __device__ __forceinline__ int64_t g_find(const GTable &t, uint64_t h, int64_t k
       uint64_t cur = rmw_load(&t.slot[s]);
       if (cur == kEmpty2) {
         if (word == kEmpty2) {
-          const uint32_t sh = tag & ((1u << t.nsh_log2) - 1);
-          const uint32_t loc = atomicAdd(&t.shard[((1u << t.nsh_log2) + sh) * 16], 1u);
+          const uint32_t sh = tag & (gb_shards(t.nsh_log2) - 1);
+          const uint32_t loc = atomicAdd(&t.shard[(gb_shards(t.nsh_log2) + sh) * 16], 1u);
           if (loc >= t.arena_sh) {
             atomicOr(&t.ctl[1], 1u);
             return -1;
@@ -139,7 +135,7 @@ __device__ __forceinline__ int64_t g_find(const GTable &t, uint64_t h, int64_t k
                   ? kEmpty2
                   : cur;
         if (cur == kEmpty2) {
-          if (atomicAdd(&t.shard[(s & ((1u << t.nsh_log2) - 1)) * 16], 1u) >= t.limit_sh) atomicOr(&t.ctl[1], 1u);
+          if (atomicAdd(&t.shard[(s & (gb_shards(t.nsh_log2) - 1)) * 16], 1u) >= t.limit_sh) atomicOr(&t.ctl[1], 1u);
           return (int64_t)s;
         }
       }
@@ -191,7 +187,7 @@ __device__ __forceinline__ bool slot_keys(const GTable &t, int nk, uint64_t s, u
 // ctl[0] = claimed groups, ctl[3] = arena entries used (sums of the shard counters)
 __global__ void gtable_sum_kernel(const GTable *__restrict__ gtp) {
   const GTable t = *gtp;
-  const uint32_t nsh = 1u << t.nsh_log2;
+  const uint32_t nsh = gb_shards(t.nsh_log2);
   uint32_t c = 0, a = 0;
   for (uint32_t i = threadIdx.x; i < nsh; i += blockDim.x) {
     c += t.shard[i * 16];

@@ -11,6 +11,7 @@ stream provider.  Every operator runs a hand-written HIP kernel in libnutexec.so
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 from dataclasses import dataclass, field
 from typing import Optional, Sequence
 
@@ -315,7 +316,10 @@ class Groups:
 
     def free(self) -> None:
         if self.h:
-            lib.nut_groups_free(self.h)
+            # nut_groups_free hands the table's allocation back to its context, which must
+            # still be there (Executor.close frees the results it still owns first)
+            if self.ex.ctx:
+                lib.nut_groups_free(self.h)
             self.h = C.c_void_p(None)
 
     def __del__(self):
@@ -338,6 +342,7 @@ class Executor:
         h = C.c_void_p()
         check(lib.nut_ctx_create(dev.index or 0, C.byref(h)), "nut_ctx_create")
         self.ctx = h
+        self._groups = weakref.WeakSet()  # results not yet freed: their tables go back to this context
         self._bind_stream()
 
     def _bind_stream(self):
@@ -346,8 +351,14 @@ class Executor:
 
     def close(self):
         if self.ctx:
+            for g in list(self._groups):  # a result freed after its context would touch freed memory
+                g.free()
             lib.nut_ctx_destroy(self.ctx)
             self.ctx = None
+
+    def _own(self, g: Groups) -> Groups:
+        self._groups.add(g)
+        return g
 
     def __del__(self):
         try:
@@ -493,7 +504,7 @@ class Executor:
         self._bind_stream()
         h = C.c_void_p()
         check(lib.nut_groupby(self.ctx, C.byref(spec), group_hint, C.byref(h)), "nut_groupby")
-        return Groups(self, h.value, max(spec.nkeys, 1), q.result_types())
+        return self._own(Groups(self, h.value, max(spec.nkeys, 1), q.result_types()))
 
     def groupby_to_host(self, q: "AggQuery | ProgQuery", group_hint: int = 0, out=None):
         """nut_groupby_to_host: (keys int64 [n, nkeys], aggs uint64 [n, naggs]) sorted by key
@@ -541,7 +552,7 @@ class Executor:
         h = C.c_void_p()
         ptrs = [C.c_void_p(_col(t, self.device)) for t in (shipdate, returnflag, linestatus, qty, price, disc)]
         check(lib.nut_q1(self.ctx, *ptrs, n, int(date_k), C.byref(h)), "nut_q1")
-        return Groups(self, h.value, 2, [np.float64, np.float64, np.float64, np.int64])
+        return self._own(Groups(self, h.value, 2, [np.float64, np.float64, np.float64, np.int64]))
 
     # ---------------------------------------------------------------- sort
     def sort_i64(self, col: torch.Tensor, out: torch.Tensor | None = None, descending: bool = False) -> torch.Tensor:

@@ -145,6 +145,36 @@ def nf_covers_all(sum_words, what=""):
     assert (s == 0).any(), what
 
 
+# ----------------------------------------------------------------------------- hash helpers
+# (shared by join_shapes.py and groupby_shapes.py: common.hpp mix64 and its inverse)
+MIX_C1, MIX_C2 = 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+INV_C1, INV_C2 = pow(MIX_C1, -1, 1 << 64), pow(MIX_C2, -1, 1 << 64)
+
+
+def _u64(x):
+    return np.atleast_1d(np.asarray(x, dtype=np.uint64))
+
+
+def mix64(z):
+    z = _u64(z)
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(MIX_C1)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(MIX_C2)
+    return z ^ (z >> np.uint64(31))
+
+
+def unmix64(z):
+    """The inverse of mix64: x ^= x >> s is undone by x ^= x >> s ^ x >> 2s (3s >= 64), the
+    odd multipliers by their inverses mod 2^64."""
+    z = _u64(z)
+    with np.errstate(over="ignore"):
+        z = z ^ (z >> np.uint64(31)) ^ (z >> np.uint64(62))
+        z = z * np.uint64(INV_C2)
+        z = z ^ (z >> np.uint64(27)) ^ (z >> np.uint64(54))
+        z = z * np.uint64(INV_C1)
+    return z ^ (z >> np.uint64(30)) ^ (z >> np.uint64(60))
+
+
 # ----------------------------------------------------------------------------- sort helpers
 # (shared by test_gpu_order_by.py and test_gpu_sort_paths.py)
 def dev(x, ex):

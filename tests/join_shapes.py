@@ -23,38 +23,14 @@ from functools import lru_cache
 
 import numpy as np
 
+from helpers import _u64, mix64, unmix64  # noqa: F401  (shared with groupby_shapes.py)
+
 I64_MIN = np.iinfo(np.int64).min
 I64_MAX = np.iinfo(np.int64).max
 HJ_SALT = 0x3C6EF372FE94F82A          # home hash = mix64(key ^ HJ_SALT)
-MIX_C1, MIX_C2 = 0xBF58476D1CE4E5B9, 0x94D049BB133111EB   # common.hpp mix64
-INV_C1, INV_C2 = pow(MIX_C1, -1, 1 << 64), pow(MIX_C2, -1, 1 << 64)
 RS = 8192                             # slots of a region (HJ_RS)
 RLIMIT = RS * 7 // 8                  # records a region-built region may hold (HJ_RLIMIT)
 TILES = (1024, 2048, 4096, 8192)      # probe tile sizes (hj_cfg, hj_any_cfg, hj_match_cfg, hj_emit_cfg)
-
-
-def _u64(x):
-    return np.atleast_1d(np.asarray(x, dtype=np.uint64))
-
-
-def mix64(z):
-    z = _u64(z)
-    with np.errstate(over="ignore"):
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(MIX_C1)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(MIX_C2)
-    return z ^ (z >> np.uint64(31))
-
-
-def unmix64(z):
-    """The inverse of mix64: x ^= x >> s is undone by x ^= x >> s ^ x >> 2s (3s >= 64), the
-    odd multipliers by their inverses mod 2^64."""
-    z = _u64(z)
-    with np.errstate(over="ignore"):
-        z = z ^ (z >> np.uint64(31)) ^ (z >> np.uint64(62))
-        z = z * np.uint64(INV_C2)
-        z = z ^ (z >> np.uint64(27)) ^ (z >> np.uint64(54))
-        z = z * np.uint64(INV_C1)
-    return z ^ (z >> np.uint64(30)) ^ (z >> np.uint64(60))
 
 
 def capacity_of(nbuild):
