@@ -593,6 +593,15 @@ typedef struct nut_groupby_layout_info {
   uint64_t owner_hash;
 } nut_groupby_layout_info;
 nut_status nut_groupby_layout(const nut_groupby_layout_query *q, nut_groupby_layout_info *out);
+/* The decoupled look-back of the compaction kernels and the join (csrc/lookback.hpp) on a
+ * chain of granules the caller constructed: status_host[ntiles] ({flag:2 | value:62}; flag
+ * 1 = a tile's own count, 2 = its inclusive prefix) is copied to the device, one wave
+ * publishes `total` for `tile` and resolves it; *excl_out = the exclusive prefix it
+ * returned, *granule_out = status[tile] afterwards.  NUT_ERR_INVALID_ARG, before anything
+ * is launched, unless tile < ntiles <= 2^24, total < 2^62 and every status_host[i], i < tile,
+ * carries flag 1 or 2: the walk then never waits.  A test hook. */
+nut_status nut_lookback_probe(nut_ctx *ctx, const uint64_t *status_host, uint64_t ntiles, uint64_t tile,
+                              uint64_t total, uint64_t *excl_out, uint64_t *granule_out);
 /* Expression-mode scan + compaction: the row ids (ascending) of the
  * rows where s->where holds — any program over s->prog_col, compiled for the query like
  * the expression-mode group-by.  Reads s->n, s->where and the program columns only (keys

@@ -196,6 +196,7 @@ SIGNATURES = {
     "nut_groupby": (_I32, [_P, C.POINTER(NutAggSpec), _U64, C.POINTER(_P)]),
     "nut_groupby_accumulate": (_I32, [_P, C.POINTER(NutAggSpec), _P]),
     "nut_groupby_layout": (_I32, [C.POINTER(NutGroupbyLayoutQuery), C.POINTER(NutGroupbyLayoutInfo)]),
+    "nut_lookback_probe": (_I32, [_P, _P, _U64, _U64, _U64, C.POINTER(_U64), C.POINTER(_U64)]),
     "nut_prog_type": (_I32, [C.POINTER(NutProg), C.POINTER(C.c_int32), _I32, C.POINTER(C.c_int32)]),
     "nut_groupby_jit_source": (_I32, [C.POINTER(NutAggSpec), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "nut_groupby_jit_compile": (_I32, [C.POINTER(NutAggSpec)]),

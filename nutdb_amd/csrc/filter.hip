@@ -265,6 +265,16 @@ __global__ __launch_bounds__(FS_THREADS, 1) void filter_i64_staged_kernel(
     tile = tn;
   }
 }
+
+// nut_lookback_probe: one wave resolves one tile over granules the host wrote
+__global__ __launch_bounds__(kWave) void lookback_probe_kernel(uint64_t *__restrict__ status, uint32_t tile,
+                                                               uint64_t total, uint32_t *__restrict__ err,
+                                                               uint64_t *__restrict__ excl_out) {
+  const int lane = threadIdx.x;
+  if (lane == 0) lookback_publish(status, tile, total);
+  const uint64_t excl = lookback_resolve(status, tile, total, err, lane);
+  if (lane == 0) *excl_out = excl;
+}
 }  // namespace nut
 
 using namespace nut;
@@ -316,6 +326,42 @@ extern "C" nut_status nut_filter_i64_async(nut_ctx *c, const int64_t *col, uint6
   }
   c->timer.end(c->stream);
   NUT_HIP(hipGetLastError());
+  return NUT_OK;
+}
+
+// A test hook: lookback_resolve on a chain of granules the caller constructed.  Every
+// predecessor must already be published (flag 1 or 2), so the walk cannot wait.
+extern "C" nut_status nut_lookback_probe(nut_ctx *c, const uint64_t *status_host, uint64_t ntiles, uint64_t tile,
+                                         uint64_t total, uint64_t *excl_out, uint64_t *granule_out) {
+  if (!c || !status_host || !excl_out || !granule_out)
+    return fail(NUT_ERR_INVALID_ARG, "nut_lookback_probe: NULL argument");
+  if (ntiles > (1ull << 24) || tile >= ntiles)
+    return fail(NUT_ERR_INVALID_ARG, "nut_lookback_probe: tile outside the granules (at most 2^24)");
+  if (total > VAL_MASK) return fail(NUT_ERR_INVALID_ARG, "nut_lookback_probe: total needs more than 62 bits");
+  for (uint64_t i = 0; i < tile; ++i) {
+    const uint64_t flag = status_host[i] >> 62;
+    if (flag != 1 && flag != 2)
+      return fail(NUT_ERR_INVALID_ARG, "nut_lookback_probe: predecessor " + std::to_string(i) + " is not published");
+  }
+  DeviceGuard g(c->device);
+  // [err u32, pad 4, excl u64][status u64 x ntiles]
+  nut_status st = c->filter_state.reserve(16 + ntiles * 8);
+  if (st) return st;
+  char *base = (char *)c->filter_state.ptr;
+  uint32_t *err = (uint32_t *)base;
+  uint64_t *excl = (uint64_t *)(base + 8);
+  uint64_t *status = (uint64_t *)(base + 16);
+  NUT_HIP(hipMemsetAsync(base, 0, 16, c->stream));
+  NUT_HIP(hipMemcpyAsync(status, status_host, ntiles * 8, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(lookback_probe_kernel, dim3(1), dim3(kWave), 0, c->stream, status, (uint32_t)tile, total, err,
+                     excl);
+  NUT_HIP(hipGetLastError());
+  NUT_HIP(hipMemcpyAsync(c->host_pinned, base, 16, hipMemcpyDeviceToHost, c->stream));
+  NUT_HIP(hipMemcpyAsync(c->host_pinned + 2, status + tile, 8, hipMemcpyDeviceToHost, c->stream));
+  NUT_HIP(hipStreamSynchronize(c->stream));
+  if ((uint32_t)c->host_pinned[0] != 0) return fail(NUT_ERR_TIMEOUT, "nut_lookback_probe: look-back spin limit hit");
+  *excl_out = c->host_pinned[1];
+  *granule_out = c->host_pinned[2];
   return NUT_OK;
 }
 

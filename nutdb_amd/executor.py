@@ -498,6 +498,17 @@ class Executor:
                                        C.c_void_p(out.data_ptr()), C.c_void_p(out_n.data_ptr())),
               "nut_filter_i64_async")
 
+    def lookback_probe(self, status, tile: int, total: int) -> tuple:
+        """nut_lookback_probe (a test hook): the look-back of `tile` over the constructed
+        granules `status` (uint64, {flag:2 | value:62}).  Returns (the exclusive prefix,
+        status[tile] as published afterwards).  A predecessor without a flag is refused."""
+        s = np.ascontiguousarray(np.asarray(status, dtype=np.uint64))
+        excl, gran = C.c_uint64(), C.c_uint64()
+        self._bind_stream()
+        check(lib.nut_lookback_probe(self.ctx, s.ctypes.data_as(C.c_void_p), len(s), int(tile), int(total),
+                                     C.byref(excl), C.byref(gran)), "nut_lookback_probe")
+        return excl.value, gran.value
+
     # ---------------------------------------------------------------- group-by
     def groupby(self, q: "AggQuery | ProgQuery", group_hint: int = 0) -> Groups:
         spec = q.to_spec(self.device)

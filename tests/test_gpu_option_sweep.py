@@ -461,13 +461,18 @@ def w_join_region(ex, orc, opts, v):
 
 # ----------------------------------------------------------------------------- scans, sort
 def w_sel_blocks(ex, orc, opts, v):
+    """300 select tiles of 16384 rows and a ragged one: with sel_blocks = 1 (a workgroup per
+    CU) there are fewer workgroups than tiles, so the option changes how many tiles a
+    workgroup takes in turn; at the default and at 16 every tile has its own."""
     def make():
         rng = np.random.default_rng(19)
-        n = 1_000_003
+        n = 300 * 16384 + 1_003
         a = rng.integers(-50, 50, n).astype(np.int64)
         b = rng.integers(0, 10, n).astype(np.int64)
         return dev(a, ex), dev(b, ex), np.flatnonzero((a > 3) & (b < 7)).astype(np.int64)
     a, b, want = cached("select", make)
+    if v == 1:
+        assert ex.info()["num_cus"] * v < 301, "sel_blocks = 1 would still give every tile its own workgroup"
     opts(sel_blocks=v)
     where = [("col", 0), ("i64", 0, 3), ("gt",), ("col", 1), ("i64", 0, 7), ("lt",), ("and",)]
     assert np.array_equal(host(ex.select_rows([a, b], where)), want)
