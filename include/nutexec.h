@@ -802,8 +802,8 @@ nut_status nut_plan_prepare(const nut_plan *plan, const nut_column *cols, int nc
 /* Execute on nrows rows of the bound columns (every column the plan names must be
  * bound).  group_hint as for nut_groupby.  Synchronous.  A plan with uncorrelated scalar
  * subqueries (`x > (SELECT avg(x) FROM t ...)`, describe: "subqueries") runs each of them
- * first over the same columns (nut_plan_execute / nut_table_execute only; the multi-table
- * entry points reject such plans with NUT_ERR_UNSUPPORTED). */
+ * first over the same columns (the multi-table entry points, raw and typed: over the FROM
+ * table, tables[0]).  A plan with a JOIN is NUT_ERR_INVALID_ARG here (nut_plan_execute2). */
 nut_status nut_plan_execute(nut_ctx *ctx, const nut_plan *plan, const nut_column *cols, int ncols,
                             uint64_t nrows, uint64_t group_hint, nut_result **out);
 /* A plan with a JOIN: `left` = the FROM table (lrows rows), `right` = the JOIN source.
@@ -825,7 +825,9 @@ nut_status nut_plan_execute2(nut_ctx *ctx, const nut_plan *plan, const nut_colum
  * reading it matches nothing there); its columns may only appear inside aggregates, which
  * skip those rows, and in scan projections (NULL there, nut_result_validity).  A SEMI /
  * ANTI step's table only filters (its columns are not output).
- * Plans with at most one JOIN are forwarded to nut_plan_execute / nut_plan_execute2. */
+ * A plan without a JOIN runs over tables[0] (one or two tables given), a plain two-table
+ * JOIN as by nut_plan_execute2 (two tables given); a UNION ALL runs branch k over tables[k]
+ * (or every branch over the one table). */
 nut_status nut_plan_executen(nut_ctx *ctx, const nut_plan *plan, const nut_column *const *tables, const int *ncols,
                              const uint64_t *nrows, int ntables, uint64_t group_hint, nut_result **out);
 /* Result = ncols output columns (the SELECT list, in order) x nrows rows. */
@@ -898,8 +900,9 @@ nut_status nut_table_execute(nut_ctx *ctx, nut_table *t, const nut_plan *plan, u
  * dictionary and decode on output; JOIN keys must be integer columns. */
 nut_status nut_table_execute2(nut_ctx *ctx, nut_table *left, nut_table *right, const nut_plan *plan,
                               uint64_t group_hint, nut_result **out);
-/* A chain of INNER joins over typed tables (tables[0] = FROM, tables[k] = the k-th JOIN
- * source; nut_plan_executen semantics).  Strings as in nut_table_execute2: filters
+/* A chain of JOINs over typed tables — INNER, LEFT / RIGHT / FULL OUTER, LEFT SEMI / ANTI
+ * steps (tables[0] = FROM, tables[k] = the k-th JOIN source; nut_plan_executen semantics,
+ * UNION ALL and plans with fewer JOINs included).  Strings as in nut_table_execute2: filters
  * (= / != / IN / LIKE), GROUP BY keys and projections use each column's own dictionary;
  * JOIN keys must be integer columns. */
 nut_status nut_table_executen(nut_ctx *ctx, nut_table *const *tables, int ntables, const nut_plan *plan,

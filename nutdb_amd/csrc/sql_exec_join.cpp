@@ -1,5 +1,5 @@
-// sql_exec_join.cpp — executing JOIN plans: one clause of any type (nut_plan_execute2) and
-// chains (nut_plan_executen), predicate pushdown, gathers into the joined table.
+// sql_exec_join.cpp — executing JOIN plans: one plain clause of any type (exec_join) and
+// chains (exec_joinn), predicate pushdown, gathers into the joined table.
 #include <array>
 
 #include "sql_plan.hpp"
@@ -173,6 +173,60 @@ const nut_plan *expand_star(const nut_plan &p, const std::vector<std::string> &n
   return &q;
 }
 
+namespace {
+
+bool in_prog(const PProg &pp, int ci) {  // (LIKE leaves read their column too)
+  for (const PNode &nd : pp)
+    if (reads_col(nd.op) && nd.col == ci) return true;
+  return false;
+}
+
+// How plan q reads column ci on the joined rows: deciding rows (WHERE, GROUP BY keys, ORDER
+// BY, projected or not), as a projection, or inside an aggregate
+struct ColUse {
+  bool row = false, proj = false, agg = false;
+  bool any() const { return row || proj || agg; }
+};
+ColUse col_use(const nut_plan &q, int ci) {
+  ColUse u;
+  u.proj = ci == q.proj;
+  for (int pj : q.projs) u.proj = u.proj || pj == ci;
+  for (const PProg &pp : q.proj_val) u.proj = u.proj || in_prog(pp, ci);
+  for (const PProg &pp : q.proj_mask) u.proj = u.proj || in_prog(pp, ci);
+  u.row = in_prog(q.where, ci);
+  for (int k : q.keys) u.row = u.row || k == ci;
+  for (const PProg &kp : q.key_progs) u.row = u.row || in_prog(kp, ci);  // computed keys
+  for (const auto &sk : q.sort_keys) u.row = u.row || sk.first == ci;
+  for (const PlanPred &pr : q.preds) u.row = u.row || pr.col == ci;
+  for (int v : q.vals) u.agg = u.agg || v == ci;
+  for (const PlanAgg &a : q.aggs) {
+    for (int ref : a.refs) u.agg = u.agg || ref == ci;
+    u.agg = u.agg || in_prog(a.val, ci) || in_prog(a.mask, ci);
+  }
+  return u;
+}
+
+// Predicate pushdown: the rows of one table (`rows` of them) that pass every conjunct of
+// conj — programs over p's columns, which src / sdict bind — as ascending row ids in `ids`,
+// *cnt of them (nut_select_rows)
+nut_status select_table_rows(nut_ctx *c, const nut_plan &p, const std::vector<PProg> &conj, const nut_column *const *src,
+                             const Dict *const *sdict, uint64_t rows, DevBuf &ids, uint64_t *cnt) {
+  nut_plan q;
+  q.compiled = true;
+  q.cols = p.cols;
+  q.where = and_all(conj);
+  nut_agg_spec spec;
+  ProgStore store;
+  std::vector<int> agg_f64;
+  nut_status es = build_spec(q, src, sdict, rows, spec, store, agg_f64);
+  if (es) return es;
+  NUT_HIP(ids.alloc(c, std::max<uint64_t>(rows, 1) * 8));
+  *cnt = 0;
+  return rows ? nut_select_rows(c, &spec, (int64_t *)ids.p, cnt) : NUT_OK;
+}
+
+}  // namespace
+
 // ldict / rdict (may be null): the dictionary of each column of lc / rc (typed tables)
 nut_status exec_join(nut_ctx *c, const nut_plan &p, const nut_column *lc, int nl, uint64_t lrows,
                      const nut_column *rc, int nr, uint64_t rrows, uint64_t hint, nut_result *r,
@@ -233,39 +287,13 @@ nut_status exec_join(nut_ctx *c, const nut_plan &p, const nut_column *lc, int nl
   const bool outer = p.join == NUT_JOIN_LEFT || full;
   // what the other (build) table may feed
   int bkey = side[k0] == ps ? k1 : k0, pkey = side[k0] == ps ? k0 : k1;
-  auto in_prog = [](const PProg &pp, int i) {  // (LIKE leaves read their column too)
-    for (const PNode &nd : pp)
-      if (reads_col(nd.op) && nd.col == i) return true;
-    return false;
-  };
-  // read by plan q after the join: as a row decider, a projection (proj NULL: counted as a
-  // row decider), or inside an aggregate
-  auto reads = [&](const nut_plan &q, int ci, bool &row, bool &agg, bool *proj = nullptr) {
-    bool pr = ci == q.proj;
-    for (int pj : q.projs) pr = pr || pj == ci;
-    for (const PProg &pp : q.proj_val) pr = pr || in_prog(pp, ci);
-    for (const PProg &pp : q.proj_mask) pr = pr || in_prog(pp, ci);
-    row = in_prog(q.where, ci);
-    if (proj) *proj = pr;
-    else row = row || pr;
-    for (int k : q.keys) row = row || k == ci;
-    for (const PProg &kp : q.key_progs) row = row || in_prog(kp, ci);  // computed keys
-    for (const auto &sk : q.sort_keys) row = row || sk.first == ci;  // ORDER BY, projected or not
-    for (const PlanPred &pr : q.preds) row = row || pr.col == ci;
-    agg = false;
-    for (int v : q.vals) agg = agg || v == ci;
-    for (const PlanAgg &a : q.aggs) {
-      for (int ref : a.refs) agg = agg || ref == ci;
-      agg = agg || in_prog(a.val, ci) || in_prog(a.mask, ci);
-    }
-  };
   // a NULL-extended table's column may feed aggregates (they skip its NULL rows) and scan
   // projections (NULL there), not WHERE / GROUP BY / ORDER BY or IS [NOT] NULL
   auto null_side = [&](int ci) { return full || (outer && side[ci] != ps); };
   for (size_t i = 0; i < nc; ++i) {
     const int ci = (int)i;
-    bool row, agg, proj;
-    reads(p, ci, row, agg, &proj);
+    const ColUse u = col_use(p, ci);
+    const bool row = u.row, agg = u.agg, proj = u.proj;
     const bool isnull = std::find(p.isnull_cols.begin(), p.isnull_cols.end(), ci) != p.isnull_cols.end();
     if (full && (row || isnull))
       return fail(NUT_ERR_PLAN, "FULL OUTER JOIN: column '" + p.cols[i] + "' may only appear inside aggregates and "
@@ -310,18 +338,8 @@ nut_status exec_join(nut_ctx *c, const nut_plan &p, const nut_column *lc, int nl
   DevBuf ids_s[2], keybuf[2];
   for (int sd = 0; sd < 2; ++sd) {
     if (push[sd].empty() || p.never) continue;
-    nut_plan q;
-    q.compiled = true;
-    q.cols = p.cols;
-    q.where = and_all(push[sd]);
-    nut_agg_spec spec;
-    ProgStore store;
-    std::vector<int> agg_f64;
-    nut_status es = build_spec(q, src.data(), sdict.data(), rows_s[sd], spec, store, agg_f64);
-    if (es) return es;
-    NUT_HIP(ids_s[sd].alloc(c, std::max<uint64_t>(rows_s[sd], 1) * 8));
     uint64_t cnt = 0;
-    if (rows_s[sd]) es = nut_select_rows(c, &spec, (int64_t *)ids_s[sd].p, &cnt);
+    nut_status es = select_table_rows(c, p, push[sd], src.data(), sdict.data(), rows_s[sd], ids_s[sd], &cnt);
     if (es) return es;
     NUT_HIP(keybuf[sd].alloc(c, std::max<uint64_t>(cnt, 1) * 8));
     es = nut_gather_u64(c, (const uint64_t *)keycol[sd]->data, (const int64_t *)ids_s[sd].p, cnt, 0,
@@ -336,11 +354,7 @@ nut_status exec_join(nut_ctx *c, const nut_plan &p, const nut_column *lc, int nl
   const int64_t *pkd = keys_s[ps], *bkd = keys_s[1 - ps];
   const uint64_t np = rows_s[ps], nb = rows_s[1 - ps];
   std::vector<char> used(nc);  // read after the join (ON-only and pushed-down columns are not)
-  for (size_t i = 0; i < nc; ++i) {
-    bool row, agg;
-    reads(p2, (int)i, row, agg);
-    used[i] = row || agg;
-  }
+  for (size_t i = 0; i < nc; ++i) used[i] = col_use(p2, (int)i).any();
   // one pass into arrays of np pairs (enough unless the build keys repeat), else again
   // with the exact count; aggregates take the pairs in any order (the unordered probe)
   const int any_order = p.kind == NUT_PLAN_GROUPBY ? NUT_JOIN_ANY_ORDER : 0;
@@ -392,11 +406,8 @@ nut_status exec_join(nut_ctx *c, const nut_plan &p, const nut_column *lc, int nl
   }
   // the joined table: every plan column gathered through its side's index
   bool proj_null = false;  // a scan projecting a NULL-extended table's column
-  for (size_t i = 0; i < nc && outer && p.kind != NUT_PLAN_GROUPBY; ++i) {
-    bool row, agg, proj;
-    reads(p2, (int)i, row, agg, &proj);
-    proj_null = proj_null || (proj && null_side((int)i));
-  }
+  for (size_t i = 0; i < nc && outer && p.kind != NUT_PLAN_GROUPBY; ++i)
+    proj_null = proj_null || (col_use(p2, (int)i).proj && null_side((int)i));
   const bool mask_col = outer && (p.kind == NUT_PLAN_GROUPBY || proj_null);
   std::vector<DevBuf> bufs(nc + 1);
   std::vector<nut_column> jc(nc + 1);
@@ -568,8 +579,8 @@ nut_status residual_semi(nut_ctx *c, const nut_plan &p, int k, int op, const nut
   return NUT_OK;
 }
 
-// A chain of INNER joins (nut_plan_executen): FROM t0 JOIN t1 ON .. JOIN t2 ON ..  Single-
-// table WHERE conjuncts are pushed down per table; the accumulated join result is kept as
+// A chain of joins (p.jn; INNER, LEFT / RIGHT / FULL OUTER, LEFT SEMI / ANTI steps): FROM t0
+// JOIN t1 ON .. JOIN t2 ON ..  Single-table WHERE conjuncts are pushed down per table; the accumulated join result is kept as
 // one row-id array per joined table (the probe side); each step builds on the next table.
 // tdicts (typed tables, nut_table_executen): per table, the dictionary of each column
 // (NULL = numeric); string columns filter, group and project with their own table's codes.
@@ -719,29 +730,6 @@ nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *ta
       return fail(NUT_ERR_PLAN, "JOIN " + std::to_string(t) + ": string keys are not executed (each table has its own "
                                     "dictionary)");
   }
-  auto in_prog = [](const PProg &pp, int i) {
-    for (const PNode &nd : pp)
-      if (reads_col(nd.op) && nd.col == i) return true;
-    return false;
-  };
-  // read by plan q after the joins: as a row decider / key, a projection, or inside an aggregate
-  auto reads = [&](const nut_plan &q, int ci, bool &row, bool &agg, bool &proj) {
-    proj = ci == q.proj;
-    for (int pj : q.projs) proj = proj || pj == ci;
-    for (const PProg &pp : q.proj_val) proj = proj || in_prog(pp, ci);
-    for (const PProg &pp : q.proj_mask) proj = proj || in_prog(pp, ci);
-    row = in_prog(q.where, ci);
-    for (int k2 : q.keys) row = row || k2 == ci;
-    for (const PProg &kp : q.key_progs) row = row || in_prog(kp, ci);  // computed keys
-    for (const auto &sk : q.sort_keys) row = row || sk.first == ci;  // ORDER BY, projected or not
-    for (const PlanPred &pr : q.preds) row = row || pr.col == ci;
-    agg = false;
-    for (int v : q.vals) agg = agg || v == ci;
-    for (const PlanAgg &a : q.aggs) {
-      for (int ref : a.refs) agg = agg || ref == ci;
-      agg = agg || in_prog(a.val, ci) || in_prog(a.mask, ci);
-    }
-  };
   // NULL-extended tables: the one a LEFT step joins, every earlier one after a RIGHT step,
   // both sides of a FULL step (their accumulated row ids hold -1 on the NULL rows; a later
   // step's ON key from such a table matches nothing there).  Their columns may only feed
@@ -760,10 +748,10 @@ nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *ta
   }
   bool proj_null = false;  // a scan projecting a NULL-extended table's column (NULL there)
   for (size_t i = 0; i < nc; ++i) {
-    bool row, agg, proj;
-    reads(p, (int)i, row, agg, proj);
+    const ColUse u = col_use(p, (int)i);
+    const bool row = u.row, proj = u.proj;
     const bool isnull = std::find(p.isnull_cols.begin(), p.isnull_cols.end(), (int)i) != p.isnull_cols.end();
-    if ((row || agg || proj) && absent[side[i]])
+    if (u.any() && absent[side[i]])
       return fail(NUT_ERR_PLAN, "SEMI / ANTI JOIN: the columns of '" + tname[side[i]] + "' are not output ('" +
                                     p.cols[i] + "')");
     if ((row || isnull) && nullable[side[i]])
@@ -794,18 +782,8 @@ nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *ta
   std::vector<uint64_t> rows(nrows, nrows + nt);
   for (int t = 0; t < nt; ++t) {
     if (push[t].empty() || p.never) continue;
-    nut_plan q;
-    q.compiled = true;
-    q.cols = p.cols;
-    q.where = and_all(push[t]);
-    nut_agg_spec spec;
-    ProgStore store;
-    std::vector<int> agg_f64;
-    nut_status es = build_spec(q, src.data(), sdict.data(), rows[t], spec, store, agg_f64);
-    if (es) return es;
-    NUT_HIP(ids[t].alloc(c, std::max<uint64_t>(rows[t], 1) * 8));
     uint64_t cnt = 0;
-    if (rows[t]) es = nut_select_rows(c, &spec, (int64_t *)ids[t].p, &cnt);
+    nut_status es = select_table_rows(c, p, push[t], src.data(), sdict.data(), rows[t], ids[t], &cnt);
     if (es) return es;
     rows[t] = cnt;
   }
@@ -945,21 +923,7 @@ nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *ta
   std::vector<DevBuf> bufs(nc);
   std::vector<nut_column> jc(nc);
   for (size_t i = 0; i < nc; ++i) {
-    const int ci = (int)i;
-    bool used = ci == p2.proj || in_prog(p2.where, ci);
-    for (int pj : p2.projs) used = used || pj == ci;
-    for (const PProg &pp : p2.proj_val) used = used || in_prog(pp, ci);
-    for (const PProg &pp : p2.proj_mask) used = used || in_prog(pp, ci);
-    for (int k2 : p2.keys) used = used || k2 == ci;
-    for (const PProg &kp : p2.key_progs) used = used || in_prog(kp, ci);  // computed GROUP BY keys
-    for (const auto &sk : p2.sort_keys) used = used || sk.first == ci;
-    for (const PlanPred &pr : p2.preds) used = used || pr.col == ci;
-    for (int v : p2.vals) used = used || v == ci;
-    for (const PlanAgg &a : p2.aggs) {
-      for (int ref : a.refs) used = used || ref == ci;
-      used = used || in_prog(a.val, ci) || in_prog(a.mask, ci);
-    }
-    if (!used || !accp[side[i]]) {
+    if (!col_use(p2, (int)i).any() || !accp[side[i]]) {  // never read, or its table's rows as they are
       jc[i] = nut_column{p.cols[i].c_str(), src[i]->data, src[i]->type};
       continue;
     }
@@ -980,11 +944,7 @@ nut_status exec_joinn(nut_ctx *c, const nut_plan &p, const nut_column *const *ta
       if (rd) reading.push_back(&a);
     }
     bool projected = false;
-    for (size_t i = 0; i < nc && proj_null; ++i) {
-      bool row, agg, proj;
-      reads(p2, (int)i, row, agg, proj);
-      projected = projected || (proj && side[i] == v);
-    }
+    for (size_t i = 0; i < nc && proj_null; ++i) projected = projected || (side[i] == v && col_use(p2, (int)i).proj);
     if (reading.empty() && !projected) continue;
     if (mbuf[v].alloc(c, std::max<uint64_t>(ncur, 1) * 8) != hipSuccess) return fail(NUT_ERR_OOM, "hipMalloc");
     if ((st = join_matched(c, accp[v], ncur, (int64_t *)mbuf[v].p))) return st;

@@ -1,6 +1,10 @@
 // sql_plan.cpp — the SQL C ABI: parse / tokenize / unescape, plan,
-// describe, prepare and execute (one table, joins, typed tables), results.  Lowering lives
-// in sql_lower.cpp, execution in sql_exec_{scan,groupby,join}.cpp (sql_plan.hpp).
+// describe, route, prepare and execute, results.  The six execute entry points (raw columns
+// or typed tables; one, two or n tables) check their arguments, wrap their tables as
+// TableViews and call one driver, run_plan, which does UNION ALL, derived tables, scalar
+// subqueries, `SELECT *`, host staging and the dispatch to the executors once; route,
+// prepare and the driver bind plan columns through one bind_columns.  Lowering lives in
+// sql_lower.cpp, execution in sql_exec_{scan,groupby,join}.cpp (sql_plan.hpp).
 #include "sql_plan.hpp"
 
 namespace {
@@ -99,26 +103,6 @@ nut_status resolve_subqueries(const nut_plan &p, nut_plan &q,
   return NUT_OK;
 }
 
-// The rest of a plan over its materialized derived table: the body's result (a group-by:
-// host columns) bound by output name as the outer plan's table (copied into HBM by the
-// call, NUT_COL_HOST).  Takes r1.
-nut_status run_over_derived(nut_ctx *c, const nut_plan &p, nut_result *r1, nut_result **out) {
-  struct Free {
-    nut_result *r;
-    ~Free() { nut_result_free(r); }
-  } f{r1};
-  if (r1->kind != NUT_PLAN_GROUPBY || r1->host.size() != r1->names.size())
-    return fail(NUT_ERR_UNSUPPORTED, "derived table: its body did not produce a group-by result");
-  std::vector<nut_column> cols;
-  for (size_t j = 0; j < r1->names.size(); ++j) {
-    if (r1->types[j] != NUT_T_I64 && r1->types[j] != NUT_T_F64) continue;  // (string outputs are not read back)
-    cols.push_back(nut_column{r1->names[j].c_str(), r1->host[j].data(), r1->types[j] | NUT_COL_HOST});
-  }
-  nut_plan o = p;
-  o.inner.reset();
-  return nut_plan_execute(c, &o, cols.data(), (int)cols.size(), r1->nrows, 0, out);
-}
-
 // UNION ALL: the branches' results in branch order as one result — device
 // columns copied after each other (scans), host columns appended (aggregates), decoded
 // strings appended, NULL flags kept per column.  Column names are branch 0's; each
@@ -199,6 +183,200 @@ nut_status concat_results(nut_ctx *c, std::vector<nut_result *> &parts, nut_resu
   }
   NUT_HIP(hipStreamSynchronize(c->stream));  // the parts' buffers are freed on return
   *out = keep.release();
+  return NUT_OK;
+}
+
+// One table as run_plan sees it: the raw nut_column arrays of nut_plan_execute*, or a typed
+// table's columns (nut_table_execute*, typed_views).
+struct TableView {
+  const nut_column *cols = nullptr;
+  int ncols = 0;
+  uint64_t nrows = 0;
+  const Dict *const *dicts = nullptr;  // per column (typed tables); null: raw columns carry no strings
+  const char *table = "";  // a typed table's name; empty: raw columns (the text and status of an unbound column)
+};
+
+// The exported function a call came through: its name begins the messages, and `tables` is
+// how many tables its signature takes (0: any number).
+struct Entry {
+  const char *name;
+  int tables;
+};
+
+// NUT_ERR_INVALID_ARG with the message "<who>: <what>"
+nut_status bad(const char *who, const std::string &what) { return fail(NUT_ERR_INVALID_ARG, std::string(who) + ": " + what); }
+nut_status bad(const Entry &e, const std::string &what) { return bad(e.name, what); }
+
+// Every plan column bound to a column of v (bind()): `SELECT *` is expanded over v's columns
+// first (into sq, and p then points at it); each column's type must be known.  An execution
+// also needs `*` to stand for something and every column to have data.  dicts (if given):
+// the bound columns' dictionaries.
+nut_status bind_columns(const char *who, const nut_plan *&p, nut_plan &sq, const TableView &v, bool executing,
+                        std::vector<const nut_column *> &bound, std::vector<const Dict *> *dicts = nullptr) {
+  if (p->star) {
+    std::vector<std::string> names;
+    for (int i = 0; i < v.ncols; ++i)
+      if (v.cols[i].name) names.push_back(v.cols[i].name);
+    if (executing && names.empty()) return bad(who, "SELECT * over no columns");
+    p = expand_star(*p, names, sq);
+  }
+  bound.assign(p->cols.size(), nullptr);
+  if (dicts) dicts->assign(p->cols.size(), nullptr);
+  for (size_t i = 0; i < p->cols.size(); ++i) {
+    const nut_column *b = bound[i] = bind(*p, (int)i, v.cols, v.ncols);
+    const std::string &name = p->cols[i];
+    if (!b)
+      return *v.table ? fail(NUT_ERR_PLAN, std::string("table '") + v.table + "' has no column '" + name + "'")
+                      : bad(who, "column '" + name + "' is not bound");
+    if (!type_known(col_type(b))) return bad(who, "column '" + name + "' has an unknown type");
+    if (executing && v.nrows && !b->data) return bad(who, "column '" + name + "' is NULL");
+    if (dicts && v.dicts) (*dicts)[i] = v.dicts[b - v.cols];
+  }
+  return NUT_OK;
+}
+
+nut_status run_plan(nut_ctx *c, const Entry &e, const nut_plan *p, const TableView *v, int nv, uint64_t hint,
+                    nut_result **out);
+
+// The rest of a plan over its materialized derived table: the body's result (a group-by:
+// host columns) bound by output name as the outer plan's one table (copied into HBM by the
+// run, NUT_COL_HOST).  Takes r1.
+nut_status run_over_derived(nut_ctx *c, const Entry &e, const nut_plan &p, nut_result *r1, nut_result **out) {
+  std::unique_ptr<nut_result, void (*)(nut_result *)> hold(r1, nut_result_free);
+  if (r1->kind != NUT_PLAN_GROUPBY || r1->host.size() != r1->names.size())
+    return fail(NUT_ERR_UNSUPPORTED, "derived table: its body did not produce a group-by result");
+  std::vector<nut_column> cols;
+  for (size_t j = 0; j < r1->names.size(); ++j) {
+    if (r1->types[j] != NUT_T_I64 && r1->types[j] != NUT_T_F64) continue;  // (string outputs are not read back)
+    cols.push_back(nut_column{r1->names[j].c_str(), r1->host[j].data(), r1->types[j] | NUT_COL_HOST});
+  }
+  nut_plan o = p;
+  o.inner.reset();
+  const TableView d{cols.data(), (int)cols.size(), r1->nrows, nullptr, ""};
+  return run_plan(c, Entry{e.name, 1}, &o, &d, 1, 0, out);
+}
+
+// Runs plan p over the tables v[0 .. nv) for entry point e: the one driver behind the six
+// nut_plan_execute* / nut_table_execute* functions.  In this order:
+//   1. UNION ALL: branch k over table k (one table: every branch over it), concatenated
+//   2. a materialized derived table / CTE: its body over the same tables (with the caller's
+//      group hint), then the rest over the body's result (hint 0)
+//   3. scalar subqueries: each over table 0 (group hint 1), then the plan with their values
+//   4. one table: `SELECT *` expanded and every plan column bound (bind_columns)
+//   5. host columns staged into HBM (they and the result of 4 live until the run returns)
+//   6. the run: exec_scan / exec_groupby over one table, exec_join for a plain two-table
+//      JOIN, exec_joinn for a chain (p->jn; one step too: ON filters, EXISTS / IN)
+// A plan without a JOIN runs over table 0 whatever nv is (up to two tables).
+nut_status run_plan(nut_ctx *c, const Entry &e, const nut_plan *p, const TableView *v, int nv, uint64_t hint,
+                    nut_result **out) {
+  const Entry one{e.name, 1};
+  *out = nullptr;
+  if (!p->uni.empty()) {
+    if (nv != 1 && (size_t)nv != p->uni.size())
+      return bad(e, "a UNION ALL of " + std::to_string(p->uni.size()) +
+                                           " branches takes one table per branch (or one for all)");
+    std::vector<nut_result *> parts;
+    for (size_t k = 0; k < p->uni.size(); ++k) {
+      nut_result *r = nullptr;
+      nut_status st = run_plan(c, one, p->uni[k].get(), &v[nv == 1 ? 0 : k], 1, hint, &r);
+      if (st) {
+        for (nut_result *x : parts) nut_result_free(x);
+        return st;
+      }
+      parts.push_back(r);
+    }
+    return concat_results(c, parts, out);
+  }
+  if (p->inner) {
+    if (e.tables == 1 && p->inner->join >= 0)
+      return bad(e, std::string("the derived table has a JOIN (") + e.name + "2)");
+    nut_result *r1 = nullptr;
+    nut_status st = run_plan(c, e, p->inner.get(), v, nv, hint, &r1);
+    return st ? st : run_over_derived(c, e, *p, r1, out);
+  }
+  // How many tables the plan takes against how many the call gave.  The raw-column entry
+  // points refuse a JOIN plan over one table and a chain through the two-table call; the
+  // typed-table ones never did: there a JOIN plan over one table fails to bind ("has no
+  // column") and a chain is counted by exec_joinn.
+  const bool raw = !*v[0].table;
+  if (p->jn.empty() && nv > 2) return bad(e, "the plan joins fewer tables");
+  const bool single = e.tables == 1 || p->join < 0 || (nv == 1 && p->jn.empty());
+  if (single && p->join >= 0 && raw) return bad(e, "the plan has a JOIN (nut_plan_execute2)");
+  if (e.tables == 2 && p->jn.size() > 1 && raw)
+    return bad(e, "the plan joins several tables (nut_plan_executen)");
+  if (!p->subs.empty()) {
+    nut_plan q;
+    nut_status st = resolve_subqueries(*p, q, [&](const nut_plan *sp, nut_result **r) {
+      return run_plan(c, one, sp, v, 1, 1, r);
+    });
+    return st ? st : run_plan(c, e, &q, v, nv, hint, out);
+  }
+  DeviceGuard g(c->device);
+  const int nt = single ? 1 : nv;
+  std::deque<HostStage> hs(nt);
+  std::vector<TableView> t(v, v + nt);
+  for (int k = 0; k < nt; ++k) {
+    nut_status st = stage_host(c, v[k].cols, v[k].ncols, v[k].nrows, hs[k], &t[k].cols);
+    if (st) return st;
+  }
+  nut_plan sq;
+  std::vector<const nut_column *> bound;
+  std::vector<const Dict *> dicts;
+  if (single) {
+    nut_status st = bind_columns(e.name, p, sq, t[0], true, bound, &dicts);
+    if (st) return st;
+  }
+  nut_result *r = new (std::nothrow) nut_result;
+  if (!r) return fail(NUT_ERR_OOM, std::string(e.name) + ": out of host memory");
+  r->kind = p->kind;
+  r->device = c->device;
+  nut_status st;
+  if (single) {
+    st = p->kind == NUT_PLAN_GROUPBY ? exec_groupby(c, *p, bound.data(), dicts.data(), t[0].nrows, hint, r)
+                                     : exec_scan(c, *p, bound.data(), dicts.data(), t[0].nrows, r);
+  } else if (p->jn.empty()) {
+    st = exec_join(c, *p, t[0].cols, t[0].ncols, t[0].nrows, t[1].cols, t[1].ncols, t[1].nrows, hint, r, t[0].dicts,
+                   t[1].dicts);
+  } else {
+    std::vector<const nut_column *> cols(nt);
+    std::vector<int> ncols(nt);
+    std::vector<uint64_t> nrows(nt);
+    std::vector<const Dict *const *> tdicts(nt);
+    for (int k = 0; k < nt; ++k) cols[k] = t[k].cols, ncols[k] = t[k].ncols, nrows[k] = t[k].nrows, tdicts[k] = t[k].dicts;
+    st = exec_joinn(c, *p, cols.data(), ncols.data(), nrows.data(), nt, hint, r, tdicts.data());
+  }
+  if (st) {
+    nut_result_free(r);
+    return st;
+  }
+  *out = r;
+  return NUT_OK;
+}
+
+// The views of typed tables: every column as a nut_column in its executed type (a Date /
+// Datetime column tells the calendar functions its kind) with its dictionary, through one
+// DictOverlays for the whole call — the query's own view of the tables' dictionaries
+// (substring results).  The tables must be whole (no ragged columns) and on c's device.
+struct TypedViews {
+  std::vector<std::vector<nut_column>> cols;
+  std::vector<std::vector<const Dict *>> dicts;
+  DictOverlays ov;
+  std::vector<TableView> views;
+};
+nut_status typed_views(const char *who, nut_ctx *c, nut_table *const *tables, int n, TypedViews &tv) {
+  tv.cols.resize(n);
+  tv.dicts.resize(n);
+  for (int k = 0; k < n; ++k) {
+    const nut_table *t = tables[k];
+    if (!t) return bad(who, "NULL table");
+    if (t->ragged()) return bad(who, "table '" + t->name + "' has ragged columns");
+    if (t->device >= 0 && t->device != c->device) return bad(who, "table '" + t->name + "' lives on another device");
+    for (const TCol &x : t->cols) {
+      tv.cols[k].push_back(nut_column{x.name.c_str(), x.dev, x.exec_type | table_kind_flag(x)});
+      tv.dicts[k].push_back(tv.ov.of(x.dict));
+    }
+    tv.views.push_back(TableView{tv.cols[k].data(), (int)tv.cols[k].size(), t->rows(), tv.dicts[k].data(), t->name.c_str()});
+  }
   return NUT_OK;
 }
 
@@ -301,19 +479,9 @@ nut_status nut_plan_route(const nut_plan *p, const nut_column *cols, int ncols, 
   if (p->join >= 0 || p->inner || !p->uni.empty() || !p->subs.empty())
     return fail(NUT_ERR_INVALID_ARG, "nut_plan_route: single-table plans without subqueries or UNION only");
   nut_plan sq;
-  if (p->star) {
-    std::vector<std::string> names;
-    for (int i = 0; i < ncols; ++i)
-      if (cols[i].name) names.push_back(cols[i].name);
-    p = expand_star(*p, names, sq);
-  }
-  std::vector<const nut_column *> bound(p->cols.size());
-  for (size_t i = 0; i < p->cols.size(); ++i) {
-    bound[i] = bind(*p, (int)i, cols, ncols);
-    if (!bound[i]) return fail(NUT_ERR_INVALID_ARG, "nut_plan_route: column '" + p->cols[i] + "' is not bound");
-    if (!type_known(col_type(bound[i])))
-      return fail(NUT_ERR_INVALID_ARG, "nut_plan_route: column '" + p->cols[i] + "' has an unknown type");
-  }
+  std::vector<const nut_column *> bound;
+  nut_status bst = bind_columns("nut_plan_route", p, sq, TableView{cols, ncols, 0, nullptr, ""}, false, bound);
+  if (bst) return bst;
   std::string route;
   if (p->kind == NUT_PLAN_GROUPBY) {
     nut_agg_spec s;
@@ -357,72 +525,13 @@ nut_status nut_plan_route(const nut_plan *p, const nut_column *cols, int ncols, 
 
 void nut_plan_free(nut_plan *p) { delete p; }
 
+// The six execute entry points: argument checks, the tables as views, run_plan.
+
 nut_status nut_plan_execute(nut_ctx *c, const nut_plan *p, const nut_column *cols, int ncols, uint64_t nrows,
                             uint64_t group_hint, nut_result **out) {
-  if (p && out && !p->uni.empty()) {  // UNION ALL: every branch over the same columns
-    *out = nullptr;
-    std::vector<nut_result *> parts;
-    for (const auto &b : p->uni) {
-      nut_result *r = nullptr;
-      nut_status st = nut_plan_execute(c, b.get(), cols, ncols, nrows, group_hint, &r);
-      if (st) {
-        for (nut_result *x : parts) nut_result_free(x);
-        return st;
-      }
-      parts.push_back(r);
-    }
-    return concat_results(c, parts, out);
-  }
   if (!c || !p || !out || (ncols && !cols) || ncols < 0) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: NULL argument");
-  *out = nullptr;
-  if (p->inner) {  // a materialized derived table: its body first, over the caller's columns
-    if (p->inner->join >= 0) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: the derived table has a JOIN (nut_plan_execute2)");
-    nut_result *r1 = nullptr;
-    nut_status st = nut_plan_execute(c, p->inner.get(), cols, ncols, nrows, group_hint, &r1);
-    return st ? st : run_over_derived(c, *p, r1, out);
-  }
-  if (p->join >= 0) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: the plan has a JOIN (nut_plan_execute2)");
-  if (!p->subs.empty()) {  // scalar subqueries first, over the same columns
-    nut_plan q;
-    nut_status st = resolve_subqueries(*p, q, [&](const nut_plan *sp, nut_result **r) {
-      return nut_plan_execute(c, sp, cols, ncols, nrows, 1, r);
-    });
-    return st ? st : nut_plan_execute(c, &q, cols, ncols, nrows, group_hint, out);
-  }
-  nut_plan sq;
-  if (p->star) {
-    std::vector<std::string> names;
-    for (int i = 0; i < ncols; ++i)
-      if (cols[i].name) names.push_back(cols[i].name);
-    if (names.empty()) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: SELECT * over no columns");
-    p = expand_star(*p, names, sq);
-  }
-  DeviceGuard g0(c->device);
-  HostStage hs;
-  nut_status hst = stage_host(c, cols, ncols, nrows, hs, &cols);
-  if (hst) return hst;
-  std::vector<const nut_column *> bound(p->cols.size());
-  for (size_t i = 0; i < p->cols.size(); ++i) {
-    bound[i] = bind(*p, (int)i, cols, ncols);
-    if (!bound[i]) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: column '" + p->cols[i] + "' is not bound");
-    if (!type_known(col_type(bound[i])))
-      return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: column '" + p->cols[i] + "' has an unknown type");
-    if (nrows && !bound[i]->data) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute: column '" + p->cols[i] + "' is NULL");
-  }
-  nut_result *r = new (std::nothrow) nut_result;
-  if (!r) return fail(NUT_ERR_OOM, "nut_plan_execute: out of host memory");
-  r->kind = p->kind;
-  r->device = c->device;
-  DeviceGuard g(c->device);
-  const std::vector<const Dict *> nodict(p->cols.size(), nullptr);  // raw columns carry no strings
-  nut_status st = p->kind == NUT_PLAN_GROUPBY ? exec_groupby(c, *p, bound.data(), nodict.data(), nrows, group_hint, r)
-                                              : exec_scan(c, *p, bound.data(), nodict.data(), nrows, r);
-  if (st) {
-    nut_result_free(r);
-    return st;
-  }
-  *out = r;
-  return NUT_OK;
+  const TableView v{cols, ncols, nrows, nullptr, ""};
+  return run_plan(c, Entry{"nut_plan_execute", 1}, p, &v, 1, group_hint, out);
 }
 
 nut_status nut_plan_execute2(nut_ctx *c, const nut_plan *p, const nut_column *left, int nleft, uint64_t lrows,
@@ -430,113 +539,20 @@ nut_status nut_plan_execute2(nut_ctx *c, const nut_plan *p, const nut_column *le
                              nut_result **out) {
   if (!c || !p || !out || (nleft && !left) || (nright && !right) || nleft < 0 || nright < 0)
     return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute2: NULL argument");
-  if (!p->uni.empty()) {  // UNION ALL of two branches: branch k over table k
-    const nut_column *tabs[2] = {left, right};
-    const int nc[2] = {nleft, nright};
-    const uint64_t nr[2] = {lrows, rrows};
-    return nut_plan_executen(c, p, tabs, nc, nr, 2, group_hint, out);
-  }
-  if (p->inner) {  // a materialized derived table over the two tables, then the rest over it
-    *out = nullptr;
-    nut_result *r1 = nullptr;
-    nut_status st = nut_plan_execute2(c, p->inner.get(), left, nleft, lrows, right, nright, rrows, group_hint, &r1);
-    return st ? st : run_over_derived(c, *p, r1, out);
-  }
-  if (p->join < 0) return nut_plan_execute(c, p, left, nleft, lrows, group_hint, out);
-  if (!p->subs.empty()) {  // scalar subqueries first, over the FROM table (left)
-    nut_plan q;
-    nut_status st = resolve_subqueries(*p, q, [&](const nut_plan *sp, nut_result **r) {
-      return nut_plan_execute(c, sp, left, nleft, lrows, 1, r);
-    });
-    return st ? st : nut_plan_execute2(c, &q, left, nleft, lrows, right, nright, rrows, group_hint, out);
-  }
-  if (p->jn.size() == 1) {  // one JOIN run as a chain step (ON filters, EXISTS / IN)
-    const nut_column *tabs[2] = {left, right};
-    const int nc[2] = {nleft, nright};
-    const uint64_t nr[2] = {lrows, rrows};
-    return nut_plan_executen(c, p, tabs, nc, nr, 2, group_hint, out);
-  }
-  if (!p->jn.empty()) return fail(NUT_ERR_INVALID_ARG, "nut_plan_execute2: the plan joins several tables (nut_plan_executen)");
-  *out = nullptr;
-  DeviceGuard g(c->device);
-  HostStage hl, hr;
-  nut_status st = stage_host(c, left, nleft, lrows, hl, &left);
-  if (!st) st = stage_host(c, right, nright, rrows, hr, &right);
-  if (st) return st;
-  nut_result *r = new (std::nothrow) nut_result;
-  if (!r) return fail(NUT_ERR_OOM, "nut_plan_execute2: out of host memory");
-  r->kind = p->kind;
-  r->device = c->device;
-  st = exec_join(c, *p, left, nleft, lrows, right, nright, rrows, group_hint, r);
-  if (st) {
-    nut_result_free(r);
-    return st;
-  }
-  *out = r;
-  return NUT_OK;
+  const TableView v[2] = {{left, nleft, lrows, nullptr, ""}, {right, nright, rrows, nullptr, ""}};
+  return run_plan(c, Entry{"nut_plan_execute2", 2}, p, v, 2, group_hint, out);
 }
 
 nut_status nut_plan_executen(nut_ctx *c, const nut_plan *p, const nut_column *const *tables, const int *ncols,
                              const uint64_t *nrows, int ntables, uint64_t group_hint, nut_result **out) {
   if (!c || !p || !out || !tables || !ncols || !nrows || ntables < 1)
     return fail(NUT_ERR_INVALID_ARG, "nut_plan_executen: NULL argument");
-  if (!p->uni.empty()) {  // UNION ALL: branch k over table k (or every branch over table 0)
-    if (ntables != 1 && (size_t)ntables != p->uni.size())
-      return fail(NUT_ERR_INVALID_ARG, "nut_plan_executen: a UNION ALL of " + std::to_string(p->uni.size()) +
-                                           " branches takes one table per branch (or one for all)");
-    *out = nullptr;
-    std::vector<nut_result *> parts;
-    for (size_t k = 0; k < p->uni.size(); ++k) {
-      const int t = ntables == 1 ? 0 : (int)k;
-      nut_result *r = nullptr;
-      nut_status st = nut_plan_execute(c, p->uni[k].get(), tables[t], ncols[t], nrows[t], group_hint, &r);
-      if (st) {
-        for (nut_result *x : parts) nut_result_free(x);
-        return st;
-      }
-      parts.push_back(r);
-    }
-    return concat_results(c, parts, out);
-  }
-  if (p->inner) {  // a materialized derived table over the tables, then the rest over it
-    *out = nullptr;
-    nut_result *r1 = nullptr;
-    nut_status st = nut_plan_executen(c, p->inner.get(), tables, ncols, nrows, ntables, group_hint, &r1);
-    return st ? st : run_over_derived(c, *p, r1, out);
-  }
-  if (p->jn.empty()) {
-    if (ntables == 1) return nut_plan_execute(c, p, tables[0], ncols[0], nrows[0], group_hint, out);
-    if (ntables == 2)
-      return nut_plan_execute2(c, p, tables[0], ncols[0], nrows[0], tables[1], ncols[1], nrows[1], group_hint, out);
-    return fail(NUT_ERR_INVALID_ARG, "nut_plan_executen: the plan joins fewer tables");
-  }
-  if (!p->subs.empty()) {  // scalar subqueries first, over the FROM table (table 0)
-    nut_plan q;
-    nut_status st = resolve_subqueries(*p, q, [&](const nut_plan *sp, nut_result **r) {
-      return nut_plan_execute(c, sp, tables[0], ncols[0], nrows[0], 1, r);
-    });
-    return st ? st : nut_plan_executen(c, &q, tables, ncols, nrows, ntables, group_hint, out);
-  }
-  *out = nullptr;
-  DeviceGuard g(c->device);
-  std::deque<HostStage> hs(ntables);
-  std::vector<const nut_column *> tabs(tables, tables + ntables);
+  std::vector<TableView> v(ntables);
   for (int k = 0; k < ntables; ++k) {
     if (ncols[k] && !tables[k]) return fail(NUT_ERR_INVALID_ARG, "nut_plan_executen: NULL table");
-    nut_status hst = stage_host(c, tables[k], ncols[k], nrows[k], hs[k], &tabs[k]);
-    if (hst) return hst;
+    v[k] = TableView{tables[k], ncols[k], nrows[k], nullptr, ""};
   }
-  nut_result *r = new (std::nothrow) nut_result;
-  if (!r) return fail(NUT_ERR_OOM, "nut_plan_executen: out of host memory");
-  r->kind = p->kind;
-  r->device = c->device;
-  nut_status st = exec_joinn(c, *p, tabs.data(), ncols, nrows, ntables, group_hint, r);
-  if (st) {
-    nut_result_free(r);
-    return st;
-  }
-  *out = r;
-  return NUT_OK;
+  return run_plan(c, Entry{"nut_plan_executen", 0}, p, v.data(), ntables, group_hint, out);
 }
 
 nut_status nut_plan_prepare(const nut_plan *p, const nut_column *cols, int ncols) {
@@ -564,28 +580,16 @@ nut_status nut_plan_prepare(const nut_plan *p, const nut_column *cols, int ncols
   // scalar subqueries: their values (int64 or f64 constants) decide the program types, so
   // the shape is compiled when the plan executes with the values in place
   if (!p->subs.empty()) return NUT_OK;
+  std::vector<nut_column> typed(cols, cols + ncols);
+  for (nut_column &col : typed) col.type &= ~NUT_COL_HOST;  // only the type matters here
   nut_plan sq;
-  if (p->star) {
-    std::vector<std::string> names;
-    for (int i = 0; i < ncols; ++i)
-      if (cols[i].name) names.push_back(cols[i].name);
-    p = expand_star(*p, names, sq);
-  }
-  std::vector<const nut_column *> bound(p->cols.size());
-  std::vector<nut_column> typed(p->cols.size());
-  for (size_t i = 0; i < p->cols.size(); ++i) {
-    bound[i] = bind(*p, (int)i, cols, ncols);
-    if (!bound[i]) return fail(NUT_ERR_INVALID_ARG, "nut_plan_prepare: column '" + p->cols[i] + "' is not bound");
-    typed[i] = *bound[i];
-    typed[i].type &= ~NUT_COL_HOST;  // only the type matters here
-    bound[i] = &typed[i];
-    if (!type_known(col_type(bound[i])))
-      return fail(NUT_ERR_INVALID_ARG, "nut_plan_prepare: column '" + p->cols[i] + "' has an unknown type");
-  }
+  std::vector<const nut_column *> bound;
+  nut_status bst = bind_columns("nut_plan_prepare", p, sq, TableView{typed.data(), ncols, 0, nullptr, ""}, false, bound);
+  if (bst) return bst;
   nut_plan nq;  // narrow columns: the expression-mode plan that executes (a Float32 key is widened there)
   if (p->kind == NUT_PLAN_GROUPBY && narrow_groupby_plan(*p, bound.data(), nq)) {
     for (int k : nq.keys)  // (a Float32 key groups on key words made at execution: compiled then)
-      if (k >= 0 && col_narrow(&typed[k])) return NUT_OK;
+      if (k >= 0 && col_narrow(bound[k])) return NUT_OK;
     p = &nq;
   }
   nut_agg_spec s;
@@ -620,195 +624,26 @@ nut_status nut_plan_prepare(const nut_plan *p, const nut_column *cols, int ncols
 
 nut_status nut_table_execute(nut_ctx *c, nut_table *t, const nut_plan *p, uint64_t group_hint, nut_result **out) {
   if (!c || !t || !p || !out) return fail(NUT_ERR_INVALID_ARG, "nut_table_execute: NULL argument");
-  *out = nullptr;
-  if (!p->uni.empty()) {  // UNION ALL: every branch over the one table
-    std::vector<nut_table *> ts(p->uni.size(), t);
-    return nut_table_executen(c, ts.data(), (int)ts.size(), p, group_hint, out);
-  }
-  if (p->inner) {  // a materialized derived table (string outputs of its body stay unread)
-    if (p->inner->join >= 0) return fail(NUT_ERR_INVALID_ARG, "nut_table_execute: the derived table has a JOIN (nut_table_execute2)");
-    nut_result *r1 = nullptr;
-    nut_status st = nut_table_execute(c, t, p->inner.get(), group_hint, &r1);
-    return st ? st : run_over_derived(c, *p, r1, out);
-  }
-  if (t->ragged()) return fail(NUT_ERR_INVALID_ARG, "nut_table_execute: table '" + t->name + "' has ragged columns");
-  if (t->device >= 0 && t->device != c->device)
-    return fail(NUT_ERR_INVALID_ARG, "nut_table_execute: the table lives on another device");
-  const uint64_t nrows = t->rows();
-  if (!p->subs.empty()) {  // scalar subqueries first, over the same table
-    nut_plan q;
-    nut_status st = resolve_subqueries(*p, q, [&](const nut_plan *sp, nut_result **r) {
-      return nut_table_execute(c, t, sp, 1, r);
-    });
-    return st ? st : nut_table_execute(c, t, &q, group_hint, out);
-  }
-  nut_plan sq;
-  if (p->star) {
-    std::vector<std::string> names;
-    for (const TCol &x : t->cols) names.push_back(x.name);
-    if (names.empty()) return fail(NUT_ERR_INVALID_ARG, "nut_table_execute: SELECT * over no columns");
-    p = expand_star(*p, names, sq);
-  }
-  std::vector<nut_column> cols(p->cols.size());
-  std::vector<const nut_column *> bound(p->cols.size());
-  std::vector<const Dict *> dicts(p->cols.size(), nullptr);
-  DictOverlays ov;  // the query's own view of the table's dictionary (substring results)
-  for (size_t i = 0; i < p->cols.size(); ++i) {
-    const TCol *tc = nullptr;
-    for (const TCol &x : t->cols)
-      if (ieq(x.name, p->cols[i])) tc = &x;
-    const size_t dot = p->cols[i].find('.');  // a qualified name: its bare column otherwise
-    for (const TCol &x : t->cols)
-      if (!tc && dot != std::string::npos && ieq(x.name, sv(p->cols[i]).substr(dot + 1))) tc = &x;
-    if (!tc) return fail(NUT_ERR_PLAN, "table '" + t->name + "' has no column '" + p->cols[i] + "'");
-    cols[i] = nut_column{tc->name.c_str(), tc->dev, tc->exec_type | table_kind_flag(*tc)};
-    bound[i] = &cols[i];
-    dicts[i] = ov.of(tc->dict);
-  }
-  nut_result *r = new (std::nothrow) nut_result;
-  if (!r) return fail(NUT_ERR_OOM, "nut_table_execute: out of host memory");
-  r->kind = p->kind;
-  r->device = c->device;
-  DeviceGuard g(c->device);
-  nut_status st = p->kind == NUT_PLAN_GROUPBY ? exec_groupby(c, *p, bound.data(), dicts.data(), nrows, group_hint, r)
-                                              : exec_scan(c, *p, bound.data(), dicts.data(), nrows, r);
-  if (st) {
-    nut_result_free(r);
-    return st;
-  }
-  *out = r;
-  return NUT_OK;
+  TypedViews tv;
+  nut_status st = typed_views("nut_table_execute", c, &t, 1, tv);
+  return st ? st : run_plan(c, Entry{"nut_table_execute", 1}, p, tv.views.data(), 1, group_hint, out);
 }
 
 nut_status nut_table_execute2(nut_ctx *c, nut_table *left, nut_table *right, const nut_plan *p, uint64_t group_hint,
                               nut_result **out) {
   if (!c || !left || !right || !p || !out) return fail(NUT_ERR_INVALID_ARG, "nut_table_execute2: NULL argument");
-  if (!p->uni.empty()) {  // UNION ALL of two branches: branch k over table k
-    nut_table *ts[2] = {left, right};
-    return nut_table_executen(c, ts, 2, p, group_hint, out);
-  }
-  if (p->inner) {
-    *out = nullptr;
-    nut_result *r1 = nullptr;
-    nut_status st = nut_table_execute2(c, left, right, p->inner.get(), group_hint, &r1);
-    return st ? st : run_over_derived(c, *p, r1, out);
-  }
-  if (p->join < 0) return nut_table_execute(c, left, p, group_hint, out);
-  if (!p->jn.empty()) {  // one JOIN run as a chain step (ON filters, EXISTS / IN)
-    nut_table *const tabs[2] = {left, right};
-    return nut_table_executen(c, tabs, 2, p, group_hint, out);
-  }
-  if (!p->subs.empty()) {  // scalar subqueries first, over the FROM table (left)
-    nut_plan q;
-    nut_status st = resolve_subqueries(*p, q, [&](const nut_plan *sp, nut_result **r) {
-      return nut_table_execute(c, left, sp, 1, r);
-    });
-    return st ? st : nut_table_execute2(c, left, right, &q, group_hint, out);
-  }
-  *out = nullptr;
-  std::vector<nut_column> cols[2];
-  std::vector<const Dict *> dicts[2];
-  DictOverlays ov;
-  nut_table *t2[2] = {left, right};
-  for (int k = 0; k < 2; ++k) {
-    nut_table *t = t2[k];
-    if (t->ragged()) return fail(NUT_ERR_INVALID_ARG, "nut_table_execute2: table '" + t->name + "' has ragged columns");
-    if (t->device >= 0 && t->device != c->device)
-      return fail(NUT_ERR_INVALID_ARG, "nut_table_execute2: table '" + t->name + "' lives on another device");
-    for (const TCol &x : t->cols) {
-      cols[k].push_back(nut_column{x.name.c_str(), x.dev, x.exec_type | table_kind_flag(x)});
-      dicts[k].push_back(ov.of(x.dict));
-    }
-  }
-  nut_result *r = new (std::nothrow) nut_result;
-  if (!r) return fail(NUT_ERR_OOM, "nut_table_execute2: out of host memory");
-  r->kind = p->kind;
-  r->device = c->device;
-  DeviceGuard g(c->device);
-  nut_status st = exec_join(c, *p, cols[0].data(), (int)cols[0].size(), left->rows(), cols[1].data(),
-                            (int)cols[1].size(), right->rows(), group_hint, r, dicts[0].data(), dicts[1].data());
-  if (st) {
-    nut_result_free(r);
-    return st;
-  }
-  *out = r;
-  return NUT_OK;
+  nut_table *const tables[2] = {left, right};
+  TypedViews tv;
+  nut_status st = typed_views("nut_table_execute2", c, tables, 2, tv);
+  return st ? st : run_plan(c, Entry{"nut_table_execute2", 2}, p, tv.views.data(), 2, group_hint, out);
 }
 
 nut_status nut_table_executen(nut_ctx *c, nut_table *const *tables, int ntables, const nut_plan *p,
                               uint64_t group_hint, nut_result **out) {
   if (!c || !tables || ntables < 1 || !p || !out) return fail(NUT_ERR_INVALID_ARG, "nut_table_executen: NULL argument");
-  for (int k = 0; k < ntables; ++k)
-    if (!tables[k]) return fail(NUT_ERR_INVALID_ARG, "nut_table_executen: NULL table");
-  if (!p->uni.empty()) {  // UNION ALL: branch k over table k (or every branch over table 0)
-    if (ntables != 1 && (size_t)ntables != p->uni.size())
-      return fail(NUT_ERR_INVALID_ARG, "nut_table_executen: a UNION ALL of " + std::to_string(p->uni.size()) +
-                                           " branches takes one table per branch (or one for all)");
-    *out = nullptr;
-    std::vector<nut_result *> parts;
-    for (size_t k = 0; k < p->uni.size(); ++k) {
-      nut_result *r = nullptr;
-      nut_status st = nut_table_execute(c, tables[ntables == 1 ? 0 : k], p->uni[k].get(), group_hint, &r);
-      if (st) {
-        for (nut_result *x : parts) nut_result_free(x);
-        return st;
-      }
-      parts.push_back(r);
-    }
-    return concat_results(c, parts, out);
-  }
-  if (p->inner) {
-    *out = nullptr;
-    nut_result *r1 = nullptr;
-    nut_status st = nut_table_executen(c, tables, ntables, p->inner.get(), group_hint, &r1);
-    return st ? st : run_over_derived(c, *p, r1, out);
-  }
-  if (p->jn.empty()) {
-    if (ntables == 1) return nut_table_execute(c, tables[0], p, group_hint, out);
-    if (ntables == 2) return nut_table_execute2(c, tables[0], tables[1], p, group_hint, out);
-    return fail(NUT_ERR_INVALID_ARG, "nut_table_executen: the plan joins fewer tables");
-  }
-  if (!p->subs.empty()) {  // scalar subqueries first, over the FROM table (table 0)
-    nut_plan q;
-    nut_status st = resolve_subqueries(*p, q, [&](const nut_plan *sp, nut_result **r) {
-      return nut_table_execute(c, tables[0], sp, 1, r);
-    });
-    return st ? st : nut_table_executen(c, tables, ntables, &q, group_hint, out);
-  }
-  *out = nullptr;
-  std::vector<std::vector<nut_column>> cols(ntables);
-  std::vector<std::vector<const Dict *>> dicts(ntables);
-  DictOverlays ov;
-  std::vector<const nut_column *> tabs(ntables);
-  std::vector<const Dict *const *> tdicts(ntables);
-  std::vector<int> ncols(ntables);
-  std::vector<uint64_t> nrows(ntables);
-  for (int k = 0; k < ntables; ++k) {
-    nut_table *t = tables[k];
-    if (t->ragged()) return fail(NUT_ERR_INVALID_ARG, "nut_table_executen: table '" + t->name + "' has ragged columns");
-    if (t->device >= 0 && t->device != c->device)
-      return fail(NUT_ERR_INVALID_ARG, "nut_table_executen: table '" + t->name + "' lives on another device");
-    for (const TCol &x : t->cols) {
-      cols[k].push_back(nut_column{x.name.c_str(), x.dev, x.exec_type | table_kind_flag(x)});
-      dicts[k].push_back(ov.of(x.dict));
-    }
-    tabs[k] = cols[k].data();
-    tdicts[k] = dicts[k].data();
-    ncols[k] = (int)cols[k].size();
-    nrows[k] = t->rows();
-  }
-  nut_result *r = new (std::nothrow) nut_result;
-  if (!r) return fail(NUT_ERR_OOM, "nut_table_executen: out of host memory");
-  r->kind = p->kind;
-  r->device = c->device;
-  DeviceGuard g(c->device);
-  nut_status st = exec_joinn(c, *p, tabs.data(), ncols.data(), nrows.data(), ntables, group_hint, r, tdicts.data());
-  if (st) {
-    nut_result_free(r);
-    return st;
-  }
-  *out = r;
-  return NUT_OK;
+  TypedViews tv;
+  nut_status st = typed_views("nut_table_executen", c, tables, ntables, tv);
+  return st ? st : run_plan(c, Entry{"nut_table_executen", 0}, p, tv.views.data(), ntables, group_hint, out);
 }
 
 nut_status nut_result_string(const nut_result *r, int j, uint64_t row, const char **str, size_t *len) {
