@@ -620,6 +620,30 @@ nut_status nut_select_jit_compile(const nut_agg_spec *s);
 nut_status nut_eval_rows(nut_ctx *ctx, const nut_agg_spec *s, const int64_t *rows, uint64_t m, uint64_t *const *out,
                          uint8_t *const *valid);
 nut_status nut_eval_jit_compile(const nut_agg_spec *s);
+/* The per-group row pick behind any / anyLast / argMin / argMax.  For each
+ * of ng groups: the position i < m of the row the order picks among the rows whose key tuple
+ * equals the group's — the smallest (want_max: largest) order value, ties to the lowest
+ * position.  order NULL: the position itself is the order (want_max 0: the first row of the
+ * group, 1: the last).  pick[g] = -1 for a group no row belongs to; a row whose tuple is not
+ * in the list is ignored.
+ *   row_keys / group_keys  host arrays of nkeys (0..2) device columns: row_keys[j][i], i < m,
+ *              and group_keys[j][g], g < ng (column-major).  The group tuples ascend strictly,
+ *              compared as SIGNED int64 words, word 0 first: the order nut_groups_to_host
+ *              returns groups in (a word with the top bit set is negative and comes first).
+ *              nkeys 0: every row belongs to the one group, and ng must be 1.
+ *   order      m device words of order_type NUT_T_I64 or NUT_T_F64; f64 is ordered by the
+ *              IEEE total order, as NUT_AGG_MIN / MAX order it (-NaN < -inf < ... < -0 < +0
+ *              < ... < +inf < +NaN).
+ *   pick       ng device words.
+ * ng >= 2^32: NUT_ERR_UNSUPPORTED; scratch (8 B per group + 4 B per row) that cannot be
+ * allocated: NUT_ERR_OOM.  Work is queued on the context's stream and the call returns after
+ * the result is complete, like nut_topk_positions.
+ *
+ * Plans (argMin(a, b), argMax(a, b), any(a), anyLast(a)) evaluate b with nut_eval_rows at every
+ * row passing WHERE, so by its rule a zero divisor in b fails the query at any such row; a
+ * is evaluated at the picked rows alone, so a zero divisor in a fails it only there. */
+nut_status nut_group_pick(nut_ctx *ctx, const int64_t *const *row_keys, int nkeys, uint64_t m, const void *order,
+                          int order_type, int want_max, const int64_t *const *group_keys, uint64_t ng, int64_t *pick);
 /* The multi-GPU join's exchange step: rows go to part (owner_hash(key) >> 56) * nparts / 256
  * (owner_hash = the group-by's; host restatement nutdb_amd/dist.py join_owner); out_keys /
  * out_rows (row0 + row index) hold the parts one after another in part order, rows
@@ -750,7 +774,8 @@ nut_status nut_sql_unescape(const char *s, size_t len, int quote, char *out, siz
  * plan's column names bound to device columns at execute time.
  *   FILTER : SELECT c FROM t [WHERE c <cmp> const]          [LIMIT]
  *   GROUPBY: SELECT k.., agg(expr).. FROM t [WHERE conj] GROUP BY k1[,k2]
- *            [ORDER BY outputs] [LIMIT]; agg in sum/count/min/max/avg
+ *            [ORDER BY outputs] [LIMIT]; agg in sum/count/min/max/avg, and
+ *            any(a) / anyLast(a) / argMin(a, b) / argMax(a, b) (nut_group_pick)
  *   SORT   : SELECT c FROM t [WHERE c <cmp> const] ORDER BY c [DESC] [LIMIT]
  * Constants may be integer/float literals, toDate('YYYY-MM-DD') and date +/-
  * interval n day|month|year (days since 1970-01-01).

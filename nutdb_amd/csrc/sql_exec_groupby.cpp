@@ -1,5 +1,6 @@
 // sql_exec_groupby.cpp — executing GROUPBY plans: packed key programs (up to 8 keys),
-// countUnique, HAVING / ORDER BY / LIMIT and arithmetic over the group result.
+// countUnique, the row picks (any / anyLast / argMin / argMax), HAVING / ORDER BY / LIMIT and
+// arithmetic over the group result.
 #include "sql_plan.hpp"
 
 namespace nut {
@@ -98,6 +99,126 @@ nut_status run_groupby(nut_ctx *c, const nut_agg_spec &s, uint64_t hint, std::ve
   return st;
 }
 
+// any / anyLast / argMin / argMax, after the main pass gave the ng sorted
+// groups and their key words kw [ng x max(nwk, 1)]: the row ids passing WHERE
+// (nut_select_rows), the key words (key_prog, the main pass's programs) and every distinct
+// order program at those rows (nut_eval_rows, NUT_MAX_AGGS programs a launch), one
+// nut_group_pick per (order, direction), and the value programs at the ng picked rows alone
+// (nut_eval_rows) into words[i * na + a].
+nut_status pick_pass(nut_ctx *c, const nut_plan &p, const nut_agg_spec &s, const GbExtra &gx, const nut_prog *key_prog,
+                     int nwk, const std::vector<int64_t> &kw, uint64_t ng, std::vector<uint64_t> &words) {
+  const size_t na = p.aggs.size();
+  // the distinct picks: (order program, direction) -> the aggregates it serves
+  struct Pick {
+    int first;  // an aggregate with this order (its programs are the pick's)
+    bool mx;
+    std::vector<int> aggs;
+  };
+  std::vector<Pick> picks;
+  for (size_t a = 0; a < na; ++a) {
+    const PlanAgg &g = p.aggs[a];
+    if (!g.pick) continue;
+    const bool mx = g.pick == PICK_ANY_LAST || g.pick == PICK_ARGMAX;
+    size_t k = 0;
+    while (k < picks.size() && !(picks[k].mx == mx && same_prog(p.aggs[picks[k].first].ord, g.ord))) ++k;
+    if (k == picks.size()) picks.push_back(Pick{(int)a, mx, {}});
+    picks[k].aggs.push_back((int)a);
+  }
+  if (picks.empty() || !ng) return NUT_OK;
+  auto oom = [](const char *what) { return fail(NUT_ERR_OOM, std::string("hipMalloc (") + what + ")"); };
+  // 1. the rows
+  uint64_t m = s.n;
+  DevBuf ids;
+  if (s.where.n) {
+    if (ids.alloc(c, s.n * 8) != hipSuccess) return oom("row pick: row ids");
+    nut_status st = nut_select_rows(c, &s, (int64_t *)ids.p, &m);
+    if (st) return st;
+  }
+  if (!m) return fail(NUT_ERR_INVALID_ARG, "row pick: groups without rows");
+  nut_agg_spec e = s;  // the programs' columns; no WHERE, no keys
+  e.where = nut_prog{0, nullptr};
+  e.nkeys = 0;
+  memset(e.agg_mask, 0, sizeof e.agg_mask);
+  auto eval = [&](const std::vector<nut_prog> &progs, const int64_t *rows, uint64_t n, std::deque<DevBuf> &out) {
+    e.naggs = (int32_t)progs.size();
+    uint64_t *ptr[NUT_MAX_AGGS];
+    for (size_t i = 0; i < progs.size(); ++i) {
+      e.agg_op[i] = NUT_AGG_SUM;
+      e.agg_val[i] = progs[i];
+      out.emplace_back();
+      if (out.back().alloc(c, n * 8) != hipSuccess) return oom("row pick: evaluated programs");
+      ptr[i] = (uint64_t *)out.back().p;
+    }
+    return nut_eval_rows(c, &e, rows, n, ptr, nullptr);
+  };
+  // 2. the key words at those rows, and the group key words column-major on the device
+  std::deque<DevBuf> kcol;
+  if (nwk) {
+    nut_status st = eval(std::vector<nut_prog>(key_prog, key_prog + nwk), (const int64_t *)ids.p, m, kcol);
+    if (st) return st;
+  }
+  std::vector<int64_t> gcol((size_t)std::max(nwk, 1) * ng);
+  for (int w = 0; w < nwk; ++w)
+    for (uint64_t i = 0; i < ng; ++i) gcol[(size_t)w * ng + i] = kw[i * nwk + w];
+  DevBuf gdev, pos;
+  if (gdev.alloc(c, gcol.size() * 8) != hipSuccess || pos.alloc(c, ng * 8) != hipSuccess) return oom("row pick: groups");
+  NUT_HIP(hipMemcpyAsync(gdev.p, gcol.data(), gcol.size() * 8, hipMemcpyHostToDevice, c->stream));
+  const int64_t *rk[NUT_MAX_KEYS] = {nullptr, nullptr}, *gk[NUT_MAX_KEYS] = {nullptr, nullptr};
+  for (int w = 0; w < nwk; ++w) {
+    rk[w] = (const int64_t *)kcol[w].p;
+    gk[w] = (const int64_t *)gdev.p + (size_t)w * ng;
+  }
+  std::vector<int64_t> rows(ng);
+  std::vector<uint64_t> col(ng);
+  for (size_t k0 = 0; k0 < picks.size();) {
+    // orders of the next picks, NUT_MAX_AGGS programs a launch (two picks may share one)
+    std::vector<nut_prog> oprog;
+    std::vector<int> of(picks.size(), -1);
+    size_t k1 = k0;
+    for (; k1 < picks.size(); ++k1) {
+      const PlanAgg &g = p.aggs[picks[k1].first];
+      if (g.ord.empty()) continue;
+      for (size_t j = k0; j < k1 && of[k1] < 0; ++j)
+        if (of[j] >= 0 && same_prog(p.aggs[picks[j].first].ord, g.ord)) of[k1] = of[j];
+      if (of[k1] >= 0) continue;
+      if (oprog.size() == NUT_MAX_AGGS) break;
+      of[k1] = (int)oprog.size();
+      oprog.push_back(gx.pk_ord[picks[k1].first]);
+    }
+    std::deque<DevBuf> ocol;
+    if (!oprog.empty()) {
+      nut_status st = eval(oprog, (const int64_t *)ids.p, m, ocol);
+      if (st) return st;
+    }
+    for (size_t k = k0; k < k1; ++k) {
+      const Pick &pk = picks[k];
+      // 3. the pick, then 4. its positions through the row ids
+      nut_status st = nut_group_pick(c, rk, nwk, m, of[k] >= 0 ? ocol[of[k]].p : nullptr,
+                                     gx.pk_ord_f64[pk.first] ? NUT_T_F64 : NUT_T_I64, pk.mx, gk, ng, (int64_t *)pos.p);
+      if (!st && ids.p) st = nut_gather_u64(c, (const uint64_t *)ids.p, (const int64_t *)pos.p, ng, ~0ull, (uint64_t *)pos.p);
+      if (st) return st;
+      NUT_HIP(hipMemcpyAsync(rows.data(), pos.p, ng * 8, hipMemcpyDeviceToHost, c->stream));
+      NUT_HIP(hipStreamSynchronize(c->stream));
+      for (int64_t r : rows)
+        if (r < 0 || (uint64_t)r >= s.n) return fail(NUT_ERR_INVALID_ARG, "row pick: a group of the main pass took no row");
+      for (size_t a0 = 0; a0 < pk.aggs.size(); a0 += NUT_MAX_AGGS) {
+        std::vector<nut_prog> vprog;
+        for (size_t j = a0; j < pk.aggs.size() && j < a0 + NUT_MAX_AGGS; ++j) vprog.push_back(gx.pk_val[pk.aggs[j]]);
+        std::deque<DevBuf> vcol;
+        st = eval(vprog, (const int64_t *)pos.p, ng, vcol);
+        if (st) return st;
+        for (size_t j = 0; j < vprog.size(); ++j) {
+          NUT_HIP(hipMemcpyAsync(col.data(), vcol[j].p, ng * 8, hipMemcpyDeviceToHost, c->stream));
+          NUT_HIP(hipStreamSynchronize(c->stream));
+          for (uint64_t i = 0; i < ng; ++i) words[i * na + pk.aggs[a0 + j]] = col[i];
+        }
+      }
+    }
+    k0 = k1;
+  }
+  return NUT_OK;
+}
+
 nut_status groupby_packed(nut_ctx *c, const nut_plan &p, const nut_agg_spec &s, const GbExtra &gx, ProgStore &store,
                           uint64_t hint, std::vector<int64_t> &keys, std::vector<uint64_t> &words, uint64_t &ng) {
   const size_t nkey = gx.key.size(), na = p.aggs.size();
@@ -186,6 +307,8 @@ nut_status groupby_packed(nut_ctx *c, const nut_plan &p, const nut_agg_spec &s, 
   for (size_t a = 0; a < na; ++a)
     if (gx.slot[a] >= 0)
       for (uint64_t i = 0; i < ng; ++i) words[i * na + a] = sw[i * m.naggs + gx.slot[a]];
+  st = pick_pass(c, p, s, gx, m.key_prog, nwk, kw, ng, words);
+  if (st) return st;
   // countUnique: GROUP BY (key words, x) -> its groups on the device -> COUNT per key words
   for (size_t ci = 0; ci < cus.size() && ng; ++ci) {
     const int a = cus[ci];
@@ -361,9 +484,11 @@ nut_status groupby_bound(nut_ctx *c, const nut_plan &p, const nut_column *const 
                             : run_groupby(c, s, hint, keys, words, ng);
   if (st) return st;
   const size_t nk = std::max<size_t>(p.keys.size(), 1), na = p.aggs.size();
-  if (p.keys.empty() && ng == 0) {
+  static const Dict kNoStrings;  // decodes every code to ''
+  const bool no_rows = p.keys.empty() && ng == 0;
+  if (no_rows) {
     // a global aggregate over no rows is still one row: counts and sums 0, min/max 0,
-    // avg NaN (ClickHouse's non-Nullable results)
+    // avg NaN, a picked value 0 or '' (ClickHouse's non-Nullable results)
     ng = 1;
     keys.assign(1, 0);
     words.assign(na + 1, 0);
@@ -392,6 +517,10 @@ nut_status groupby_bound(nut_ctx *c, const nut_plan &p, const nut_column *const 
     } else if (o.kind == OUT_AGG) {
       type = agg_f64[o.a] ? NUT_T_F64 : NUT_T_I64;
       for (uint64_t i = 0; i < ng; ++i) col[i] = words[i * na + o.a];
+      if (gx.pk_dict[o.a] >= 0) {  // any / argMax / .. of a string column: its codes, decoded at the end
+        type = NUT_T_STR;
+        out_dict[j] = no_rows ? &kNoStrings : dicts[gx.pk_dict[o.a]];
+      }
     } else {
       type = NUT_T_F64;
       for (uint64_t i = 0; i < ng; ++i) {

@@ -51,7 +51,7 @@ bool needs_key_progs(const nut_plan &p) {
   for (int k : p.keys)
     if (k < 0) return true;
   for (const PlanAgg &a : p.aggs)
-    if (a.distinct) return true;
+    if (a.distinct || a.pick) return true;
   return false;
 }
 
@@ -538,6 +538,10 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
     gx->key.clear();
     gx->cu_val.assign(p.aggs.size(), nut_prog{0, nullptr});
     gx->cu_mask.assign(p.aggs.size(), nut_prog{0, nullptr});
+    gx->pk_val.assign(p.aggs.size(), nut_prog{0, nullptr});
+    gx->pk_ord.assign(p.aggs.size(), nut_prog{0, nullptr});
+    gx->pk_ord_f64.assign(p.aggs.size(), 0);
+    gx->pk_dict.assign(p.aggs.size(), -1);
   }
   s.nkeys = keyprog ? 0 : (int32_t)p.keys.size();
   for (size_t j = 0; j < p.keys.size() && !keyprog; ++j) {
@@ -646,7 +650,7 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
     };
     {
       std::vector<const PProg *> all{&p.where};
-      for (const PlanAgg &g : p.aggs) all.push_back(&g.val), all.push_back(&g.mask);
+      for (const PlanAgg &g : p.aggs) all.push_back(&g.val), all.push_back(&g.mask), all.push_back(&g.ord);
       for (const PProg &k : p.key_progs) all.push_back(&k);
       for (const PProg *pp : all)
         for (const PNode &nd : *pp)
@@ -813,6 +817,22 @@ nut_status build_spec(const nut_plan &p, const nut_column *const *bound, const D
         if (!st && t == NUT_PT_F64) st = fail(NUT_ERR_PLAN, "countUnique of a float64 expression is not executed");
         if (!st && g.val.size() != 1 && dicts) st = check_strings(p, g.val, dicts, "countUnique argument");
         if (!st && !g.mask.empty()) st = resolve(g.mask, gx->cu_mask[a], "countUnique argument", &t);
+        continue;
+      }
+      if (g.pick) {  // any / anyLast / argMin / argMax: its own pass (exec_groupby)
+        if (!gx) continue;
+        const std::string f = pick_name(g.pick);
+        // the value: a number, or one string column (decoded through its dictionary)
+        const bool str_val = g.val.size() == 1 && g.val[0].op == NUT_P_COL && dicts && dicts[g.val[0].col];
+        st = resolve(g.val, gx->pk_val[a], (f + " value").c_str(), &t, str_val);
+        if (str_val) gx->pk_dict[a] = g.val[0].col;
+        agg_f64[a] = !st && t == NUT_PT_F64;
+        if (st || g.ord.empty()) continue;
+        if (g.ord.size() == 1 && g.ord[0].op == NUT_P_COL && dicts && dicts[g.ord[0].col])
+          st = fail(NUT_ERR_PLAN, f + ": the order '" + p.cols[g.ord[0].col] + "' is a string column (an order is an "
+                                      "int64, bool or float64 value)");
+        if (!st) st = resolve(g.ord, gx->pk_ord[a], (f + " order").c_str(), &t);
+        gx->pk_ord_f64[a] = !st && t == NUT_PT_F64;
         continue;
       }
       const int k = s.naggs++;

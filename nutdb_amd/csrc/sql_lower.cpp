@@ -846,6 +846,15 @@ void bind_str(PProg &a, const PProg &other) {
 bool is_agg_name(sv n) {
   return ieq(n, "sum") || ieq(n, "count") || ieq(n, "min") || ieq(n, "max") || ieq(n, "avg");
 }
+// any / anyLast / argMin / argMax (a value of a picked row): PickKind, else 0
+int pick_kind(sv n) {
+  return ieq(n, "any") ? PICK_ANY : ieq(n, "anylast") ? PICK_ANY_LAST : ieq(n, "argmin") ? PICK_ARGMIN
+         : ieq(n, "argmax") ? PICK_ARGMAX : PICK_NO;
+}
+const char *pick_name(int kind) {
+  static const char *names[] = {"", "any", "anyLast", "argMin", "argMax"};
+  return names[kind];
+}
 
 // A conditional: conds[i] -> vals[i], else vals.back().  CASE WHEN / IF / multiIf and
 // CASE x WHEN v (cond x = v).  Returns false if e is not a conditional.
@@ -1045,7 +1054,8 @@ bool lower_prog(nut_plan &p, const Expr &e, PProg &o, Lowering &L) {
       if (f != FnKind::Others) return L.fail("'" + expr_text(e) + "' (EXISTS / subqueries) is not executed");
       const sv n = e.id.name;
       const size_t na = e.kids.size();
-      if (is_agg_name(n)) return L.fail("aggregate '" + std::string(n) + "' nested inside an expression");
+      if (is_agg_name(n) || pick_kind(n))
+        return L.fail("aggregate '" + std::string(n) + "' nested inside an expression");
       if ((ieq(n, "abs") || ieq(n, "tofloat64")) && na == 1) {
         if (!lower_prog(p, e.kids[0], o, L)) return false;
         emit(o, ieq(n, "abs") ? NUT_P_ABS : NUT_P_TO_F64);
@@ -1221,7 +1231,8 @@ int add_agg(nut_plan &p, const PlanAgg &a) {
   for (size_t i = 0; i < p.aggs.size(); ++i) {
     const PlanAgg &b = p.aggs[i];
     if (p.compiled) {
-      if (b.op == a.op && b.distinct == a.distinct && same_prog(b.mask, a.mask) &&
+      if (b.op == a.op && b.distinct == a.distinct && b.pick == a.pick && same_prog(b.ord, a.ord) &&
+          same_prog(b.mask, a.mask) &&
           (a.op == NUT_AGG_COUNT || same_prog(b.val, a.val)) && (!a.distinct || same_prog(b.val, a.val)) &&
           (b.refs == a.refs || (a.op == NUT_AGG_COUNT && !a.distinct && !outer)))
         return (int)i;
@@ -1310,7 +1321,7 @@ int key_of(nut_plan &p, const Expr &e) {
 bool is_distinct_name(sv n) { return ieq(n, "countunique") || ieq(n, "uniqexact") || ieq(n, "uniq"); }
 bool is_output_leaf(nut_plan &p, const Expr &e) {
   return key_of(p, e) >= 0 ||
-         (e.k == EK::FnCall && e.fn() == FnKind::Others && (is_agg_name(e.id.name) || is_distinct_name(e.id.name)));
+         (e.k == EK::FnCall && e.fn() == FnKind::Others && (is_agg_name(e.id.name) || is_distinct_name(e.id.name) || pick_kind(e.id.name)));
 }
 bool having_output(nut_plan &p, const Expr &e, int &out, Lowering &L);
 
@@ -1395,7 +1406,7 @@ bool lower_output(nut_plan &p, const Expr &e, PlanOut &o, Lowering &L) {
   if (column_ref(p, e, name))
     return L.fail("column '" + std::string(name) + "' is neither a GROUP BY key nor aggregated" +
                   (p.keys.empty() ? " (no GROUP BY)" : ""));
-  if (!(e.k == EK::FnCall && e.fn() == FnKind::Others && (is_agg_name(e.id.name) || is_distinct_name(e.id.name)))) {
+  if (!(e.k == EK::FnCall && e.fn() == FnKind::Others && (is_agg_name(e.id.name) || is_distinct_name(e.id.name) || pick_kind(e.id.name)))) {
     XNode x;
     if (!lower_xpr(p, e, x, L)) return false;
     p.xprs.push_back(std::move(x));
@@ -1420,6 +1431,36 @@ bool lower_output(nut_plan &p, const Expr &e, PlanOut &o, Lowering &L) {
     a.op = NUT_AGG_COUNT;
     a.expr = NUT_EX_COL;
     a.distinct = true;
+    o.kind = OUT_AGG;
+    o.a = add_agg(p, a);
+    return true;
+  }
+  if (const int pk = pick_kind(fn)) {
+    // any(x) / anyLast(x) / argMin(x, b) / argMax(x, b): x at the row of the group that b (or
+    // the table order) picks — a pass of its own after the main one (exec_groupby, §3.14)
+    const std::string f = pick_name(pk);
+    if (!p.compiled) return L.fail(f + " runs in expression mode");
+    if (p.join >= 0 || !p.jn.empty())
+      return L.fail(f + " over a JOIN (or an EXISTS / IN subquery) is not executed: the joined rows have no table order");
+    const size_t want = pk >= PICK_ARGMIN ? 2 : 1;
+    if (e.kids.size() != want)
+      return L.fail(f + (want == 2 ? " takes two arguments (the value, then the order)" : " takes one argument"));
+    PlanAgg a{};
+    for (size_t j = 0; j < want; ++j) {
+      PProg mask;
+      bool nullable = false;
+      if (!lower_nullable(p, e.kids[j], j ? a.ord : a.val, mask, nullable, L)) return false;
+      if (nullable)
+        return L.fail(f + ": a NULL branch (CASE without ELSE) in '" + expr_text(e.kids[j]) + "' is not executed");
+    }
+    for (const PProg *pp : {&a.val, &a.ord})
+      for (const PNode &nd : *pp)
+        if (reads_col(nd.op)) a.refs.push_back(nd.col);
+    std::sort(a.refs.begin(), a.refs.end());
+    a.refs.erase(std::unique(a.refs.begin(), a.refs.end()), a.refs.end());
+    a.op = NUT_AGG_MIN;
+    a.expr = NUT_EX_COL;
+    a.pick = pk;
     o.kind = OUT_AGG;
     o.a = add_agg(p, a);
     return true;
@@ -1919,7 +1960,7 @@ bool lower_mode(const Query &qry, nut_plan &p, Lowering &L) {
   // an aggregate anywhere in a SELECT item (sum(a) / sum(b) too); other functions
   // (abs, toYYYYMMDD, ...) are computed projections of a scan
   std::function<bool(const Expr &)> contains_agg = [&](const Expr &e) {
-    if (e.k == EK::FnCall && e.fn() == FnKind::Others && (is_agg_name(e.id.name) || is_distinct_name(e.id.name)))
+    if (e.k == EK::FnCall && e.fn() == FnKind::Others && (is_agg_name(e.id.name) || is_distinct_name(e.id.name) || pick_kind(e.id.name)))
       return true;
     if (e.k == EK::Subquery) return false;
     for (const Expr &k : e.kids)
@@ -2227,7 +2268,7 @@ bool flatten_derived(const Query &q, std::unique_ptr<Query> &flat, Lowering &L) 
   // the body's outputs by name: its alias, or a column's own name
   std::vector<std::pair<sv, const Expr *>> outs;
   std::function<bool(const Expr &)> has_agg = [&](const Expr &e) {
-    if (e.k == EK::FnCall && e.fn() == FnKind::Others && is_agg_name(e.id.name)) return true;
+    if (e.k == EK::FnCall && e.fn() == FnKind::Others && (is_agg_name(e.id.name) || pick_kind(e.id.name))) return true;
     for (const Expr &k : e.kids)
       if (has_agg(k)) return true;
     return false;
@@ -2310,7 +2351,7 @@ bool flatten_derived(const Query &q, std::unique_ptr<Query> &flat, Lowering &L) 
 // outer query reads it alone (no JOIN), by name, as its own table
 bool grouped_body(const QueryBody &in) {
   std::function<bool(const Expr &)> has_agg = [&](const Expr &e) {
-    if (e.k == EK::FnCall && e.fn() == FnKind::Others && is_agg_name(e.id.name)) return true;
+    if (e.k == EK::FnCall && e.fn() == FnKind::Others && (is_agg_name(e.id.name) || pick_kind(e.id.name))) return true;
     for (const Expr &k : e.kids)
       if (has_agg(k)) return true;
     return false;
@@ -2579,8 +2620,12 @@ std::string describe(const nut_plan &p) {
       const PlanAgg &a = p.aggs[i];
       if (i) o += ',';
       o += "{\"op\":\"";
-      o += a.distinct ? "count_distinct" : aggs[a.op];
+      o += a.distinct ? "count_distinct" : a.pick ? pick_name(a.pick) : aggs[a.op];
       o += "\"";
+      if (a.pick >= PICK_ARGMIN) {
+        o += ",\"order\":";
+        json_str(o, prog_text(p, a.ord));
+      }
       if (a.distinct) {
         o += ",\"expr\":";
         json_str(o, prog_text(p, a.val));

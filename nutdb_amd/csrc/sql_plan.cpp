@@ -81,7 +81,7 @@ nut_status resolve_subqueries(const nut_plan &p, nut_plan &q,
   for (PProg &pp : q.proj_val) prog(pp);
   for (PProg &pp : q.proj_mask) prog(pp);
   for (PProg &pp : q.key_progs) prog(pp);
-  for (PlanAgg &a : q.aggs) prog(a.val), prog(a.mask);
+  for (PlanAgg &a : q.aggs) prog(a.val), prog(a.mask), prog(a.ord);
   for (nut_plan::JoinStep &js : q.jn) prog(js.cond);
   std::function<void(HNode &)> hv = [&](HNode &h) {
     if (h.k == H_CONST && h.param >= 0) {

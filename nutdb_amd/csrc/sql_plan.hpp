@@ -76,7 +76,13 @@ struct PlanAgg {
   PProg val, mask;        // compiled mode: argument program and row mask (empty = every row)
   std::vector<int> refs;  // compiled mode: columns the argument reads (COUNT(x) included)
   bool distinct = false;  // countUnique(val): distinct values per group (op COUNT; two passes)
+  // any / anyLast / argMin / argMax: val at the row of the group that ord
+  // picks (PickKind; op MIN, never run as one).  ord is empty for any / anyLast.
+  int pick = 0;
+  PProg ord;
 };
+// PlanAgg::pick: the value at the group's first / last row, or at its row of least / greatest ord
+enum PickKind { PICK_NO = 0, PICK_ANY = 1, PICK_ANY_LAST = 2, PICK_ARGMIN = 3, PICK_ARGMAX = 4 };
 // Arithmetic over a group's outputs (SELECT sum(a) / count(), 100 * sum(x) / sum(y), ...),
 // evaluated on the host per result group with nut_prog semantics: int + - * wrap, an f64
 // operand makes the op f64, / is always f64, % and intDiv truncate (a zero divisor fails).
@@ -324,10 +330,14 @@ struct ProgStore {
 // Key programs and countUnique arguments of a compiled aggregate plan, resolved against
 // the spec's program columns (exec_groupby packs them into key words)
 struct GbExtra {
-  bool active = false;            // keys are programs: computed keys, > 2 keys or countUnique
-  std::vector<int> slot;          // plan aggregate -> spec aggregate (-1: countUnique)
+  bool active = false;            // keys are programs: computed keys, > 2 keys, countUnique or a row pick
+  std::vector<int> slot;          // plan aggregate -> spec aggregate (-1: countUnique, row picks)
   std::vector<nut_prog> key;      // per GROUP BY key
   std::vector<nut_prog> cu_val, cu_mask;  // per plan aggregate (countUnique only)
+  // row picks (PlanAgg::pick), per plan aggregate: the value and order programs, whether the
+  // order is float64, and the plan column whose dictionary decodes a string value (else -1)
+  std::vector<nut_prog> pk_val, pk_ord;
+  std::vector<int> pk_ord_f64, pk_dict;
 };
 // HAVING evaluation for group i: operands are int64 or f64 output words / constants;
 // int-int comparisons are exact, anything else compares as f64
@@ -431,6 +441,8 @@ bool lower_pred_term(nut_plan &p, const Expr &e, Lowering &L);
 bool lower_where(nut_plan &p, const Expr &e, Lowering &L);
 int key_of(nut_plan &p, const Expr &e);
 bool is_distinct_name(sv n);
+int pick_kind(sv n);
+const char *pick_name(int kind);
 bool is_output_leaf(nut_plan &p, const Expr &e);
 bool lower_xpr(nut_plan &p, const Expr &e, XNode &x, Lowering &L);
 bool lower_output(nut_plan &p, const Expr &e, PlanOut &o, Lowering &L);

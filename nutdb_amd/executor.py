@@ -684,6 +684,46 @@ class Executor:
                                 m, po, pv), "nut_eval_rows")
         return [o[:m] for o in outs], [v[:m] for v in valid]
 
+    # the launch shape of nut_group_pick's kernels (csrc/pick.hpp): threads per workgroup,
+    # rows a workgroup takes per step
+    PICK_THREADS, PICK_TILE = 256, 1024
+
+    def group_pick(self, row_keys: list, order: torch.Tensor | None, group_keys: list,
+                   want_max: bool = False, nrows: int | None = None) -> torch.Tensor:
+        """The per-group row pick behind any / anyLast / argMin / argMax (nut_group_pick):
+        row_keys = 0..2 int64 key-word columns of the m rows, group_keys = as many columns of
+        the ng group tuples (strictly ascending, signed, word 0 first; no keys: one group),
+        order = m int64 / float64 order values or None (the position is the order).  Returns
+        an int64 tensor of ng positions: the row of the least (want_max: greatest) order per
+        group, ties to the lowest position, -1 for a group without rows.  nrows: the row count
+        when neither a key nor an order column gives it."""
+        nk = len(row_keys)
+        if len(group_keys) != nk:
+            raise ValueError("group_pick takes as many group key columns as row key columns")
+        cols = list(row_keys) + list(group_keys) + ([order] if order is not None else [])
+        if any(t.dtype != torch.int64 for t in cols[:2 * nk]):
+            raise TypeError("group_pick takes int64 key words")
+        if order is not None and order.dtype not in (torch.int64, torch.float64):
+            raise TypeError("group_pick orders by an int64 or float64 column")
+        if nk:
+            m, ng = row_keys[0].numel(), group_keys[0].numel()
+        else:
+            if order is None and nrows is None:
+                raise ValueError("group_pick without keys and order needs nrows")
+            m, ng = order.numel() if order is not None else int(nrows), 1
+        if any(t.numel() != m for t in row_keys) or any(t.numel() != ng for t in group_keys) or \
+                (order is not None and order.numel() != m):
+            raise ValueError("group_pick: columns of different lengths")
+        ptrs = [_col(t, self.device) if t.numel() else None for t in cols]
+        rk = (C.c_void_p * max(nk, 1))(*ptrs[:nk])
+        gk = (C.c_void_p * max(nk, 1))(*ptrs[nk:2 * nk])
+        out = torch.empty(max(ng, 1), dtype=torch.int64, device=self.device)
+        self._bind_stream()
+        check(lib.nut_group_pick(self.ctx, rk, nk, m, C.c_void_p(ptrs[2 * nk] if order is not None else None),
+                                 L.T_F64 if order is not None and order.dtype == torch.float64 else L.T_I64,
+                                 int(bool(want_max)), gk, ng, C.c_void_p(out.data_ptr())), "nut_group_pick")
+        return out[:ng]
+
     def partition_i64(self, col: torch.Tensor, splitters, out: torch.Tensor | None = None):
         """Stable partition by bucket(k) = #{splitters <= k} (nut_partition_i64).  Returns
         (partitioned tensor, per-bucket counts)."""
