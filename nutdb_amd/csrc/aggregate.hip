@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -545,13 +546,56 @@ struct GpMeta {
   }
 };
 
-uint32_t gp_tiles(std::vector<GpSeg> &segs, uint32_t tile, std::vector<uint32_t> &ts) {
-  ts.clear();
-  for (uint32_t i = 0; i < segs.size(); ++i) {
-    segs[i].tile0 = (uint32_t)ts.size();
-    ts.insert(ts.end(), (segs[i].count + tile - 1) / tile, i);
+GpArrays gp_arrays(const uint64_t *const *src, uint64_t *const *dst, int narr) {
+  GpArrays ar;
+  for (int a = 0; a < GP_MAX_ARR; ++a) {
+    ar.src[a] = src[a];
+    ar.dst[a] = dst[a];
   }
-  return (uint32_t)ts.size();
+  ar.narr = narr;
+  return ar;
+}
+
+// value columns the aggregates read, each partitioned once: vmap[j] is the staged array of
+// the caller's value column j (-1: no aggregate reads it), src the arrays the first
+// partition level reads ([1] k1, [2] k2, [3 + vmap[j]] the values)
+struct StagedCols {
+  int vmap[NUT_MAX_VALS];
+  int nv = 0;
+  const uint64_t *src[GP_MAX_ARR] = {};
+};
+StagedCols staged_cols(const nut_agg_spec *s, int nk) {
+  StagedCols sc;
+  for (int j = 0; j < NUT_MAX_VALS; ++j) sc.vmap[j] = -1;
+  for (int a = 0; a < s->naggs; ++a)
+    if (s->agg_op[a] != NUT_AGG_COUNT && sc.vmap[s->agg_arg[a][0]] < 0) sc.vmap[s->agg_arg[a][0]] = sc.nv++;
+  sc.src[1] = (const uint64_t *)s->keys[0];
+  sc.src[2] = nk == 2 ? (const uint64_t *)s->keys[1] : nullptr;
+  for (int j = 0; j < NUT_MAX_VALS; ++j)
+    if (sc.vmap[j] >= 0) sc.src[3 + sc.vmap[j]] = (const uint64_t *)s->val_col[j];
+  return sc;
+}
+// s's aggregates over n rows of the staged arrays `arr` (laid out as StagedCols::src)
+nut_agg_spec staged_spec(const nut_agg_spec *s, const StagedCols &sc, int nk, uint64_t n, uint64_t *const *arr) {
+  nut_agg_spec s2;
+  memset(&s2, 0, sizeof(s2));
+  s2.n = n;  // (segment mode reads only the listed ranges)
+  s2.nkeys = nk;
+  s2.keys[0] = (const int64_t *)arr[1];
+  s2.keys[1] = nk == 2 ? (const int64_t *)arr[2] : nullptr;
+  s2.nvals = sc.nv;
+  s2.naggs = s->naggs;
+  for (int j = 0; j < NUT_MAX_VALS; ++j)
+    if (sc.vmap[j] >= 0) {
+      s2.val_col[sc.vmap[j]] = arr[3 + sc.vmap[j]];
+      s2.val_type[sc.vmap[j]] = s->val_type[j];
+    }
+  for (int a = 0; a < s->naggs; ++a) {
+    s2.agg_op[a] = s->agg_op[a];
+    s2.agg_expr[a] = NUT_EX_COL;
+    if (s->agg_op[a] != NUT_AGG_COUNT) s2.agg_arg[a][0] = sc.vmap[s->agg_arg[a][0]];
+  }
+  return s2;
 }
 
 // the capped scatter launch (no histogram; see gp_level): hash digits, or range digits of
@@ -631,12 +675,7 @@ nut_status gp_level(nut_ctx *c, GpMeta &mm, std::vector<GpSeg> &segs, int shift,
       dcut = (unsigned long long *)mm.alloc(nc * 8);
       NUT_HIP(hipMemsetAsync(dcut, 0xff, nc * 8, st));
     }
-    GpArrays ar;
-    for (int a = 0; a < GP_MAX_ARR; ++a) {
-      ar.src[a] = src[a];
-      ar.dst[a] = dst[a];
-    }
-    ar.narr = narr;
+    const GpArrays ar = gp_arrays(src, dst, narr);
     unsigned long long *dflag = (unsigned long long *)dcur + nc;
     gp_capped_launch(c, ar, dseg, dts, nst, shift, (unsigned long long *)dcur, kx, ovf, dflag, bits, src[2] != nullptr,
                      rg, acur, acap, dcut, gather ? 1 : 0);
@@ -699,12 +738,7 @@ nut_status gp_level(nut_ctx *c, GpMeta &mm, std::vector<GpSeg> &segs, int shift,
   if (s) return s;
   uint64_t *dcur;
   if ((s = mm.up(segs, &dseg)) || (s = mm.up(ts, &dts)) || (s = mm.up(cur, &dcur))) return s;
-  GpArrays ar;
-  for (int a = 0; a < GP_MAX_ARR; ++a) {
-    ar.src[a] = src[a];
-    ar.dst[a] = dst[a];
-  }
-  ar.narr = narr;
+  const GpArrays ar = gp_arrays(src, dst, narr);
   if (nst) {
     const unsigned grid = std::min<unsigned>(nst, (unsigned)c->num_cus);
     if (src[2])
@@ -782,15 +816,11 @@ nut_status gp_aggregate(nut_groups *g, GpMeta &mm, const std::vector<uint64_t> &
 nut_status groupby_partitioned_direct(nut_groups *g, const nut_agg_spec *s, uint64_t group_hint) {
   nut_ctx *c = g->ctx;
   hipStream_t st = c->stream;
-  const int nk = g->nk, na = g->naggs;
+  const int nk = g->nk;
   const uint64_t n = s->n;
-  // value columns the aggregates read, each partitioned once
-  int vmap[NUT_MAX_VALS];
-  int nv = 0;
-  for (int j = 0; j < NUT_MAX_VALS; ++j) vmap[j] = -1;
-  for (int a = 0; a < na; ++a)
-    if (s->agg_op[a] != NUT_AGG_COUNT && vmap[s->agg_arg[a][0]] < 0) vmap[s->agg_arg[a][0]] = nv++;
-  const int narr = 3 + nv;
+  const StagedCols sc = staged_cols(s, nk);
+  const uint64_t *const *src = sc.src;
+  const int narr = 3 + sc.nv;
   const uint64_t rows = (n + 2 * 65536 + 64 + 31) & ~31ull;  // + one alignment gap per partition
   const int nstore = narr - 1 - (nk == 1 ? 1 : 0);
   const int levels = gb_levels(group_hint, (int)c->opt[NUT_OPT_GB_LEVELS]);
@@ -832,11 +862,6 @@ nut_status groupby_partitioned_direct(nut_groups *g, const nut_agg_spec *s, uint
   // share of rows (the rows after the partitions take overflowing runs: at least one tile),
   // so only a key hash skewed that far falls back to the histogram layout (8-bit digits)
   const uint64_t ocap = ((2 * rows - 2 * GP_TILE) >> bits0) & ~1ull;
-  const uint64_t *src[GP_MAX_ARR] = {};
-  src[1] = (const uint64_t *)s->keys[0];
-  src[2] = nk == 2 ? (const uint64_t *)s->keys[1] : nullptr;
-  for (int j = 0; j < NUT_MAX_VALS; ++j)
-    if (vmap[j] >= 0) src[3 + vmap[j]] = (const uint64_t *)s->val_col[j];
   GpMeta mm{c};
   c->timer.begin(st, NUT_KERNEL_AGGREGATE);
   std::vector<GpSeg> segs{GpSeg{0, n, 0, 0}};
@@ -903,25 +928,7 @@ nut_status groupby_partitioned_direct(nut_groups *g, const nut_agg_spec *s, uint
     if (e) return e;
   }
   c->timer.end(st);
-  nut_agg_spec s2;
-  memset(&s2, 0, sizeof(s2));
-  s2.n = n;  // (segment mode reads only the listed ranges)
-  s2.nkeys = nk;
-  s2.keys[0] = (const int64_t *)fin[1];
-  s2.keys[1] = nk == 2 ? (const int64_t *)fin[2] : nullptr;
-  s2.nvals = nv;
-  s2.naggs = na;
-  for (int j = 0; j < NUT_MAX_VALS; ++j)
-    if (vmap[j] >= 0) {
-      s2.val_col[vmap[j]] = fin[3 + vmap[j]];
-      s2.val_type[vmap[j]] = s->val_type[j];
-    }
-  for (int a = 0; a < na; ++a) {
-    s2.agg_op[a] = s->agg_op[a];
-    s2.agg_expr[a] = NUT_EX_COL;
-    if (s->agg_op[a] != NUT_AGG_COUNT) s2.agg_arg[a][0] = vmap[s->agg_arg[a][0]];
-  }
-  return gp_aggregate(g, mm, parts, s2, g->kinds, group_hint);
+  return gp_aggregate(g, mm, parts, staged_spec(s, sc, nk, n, fin), g->kinds, group_hint);
 }
 
 // ------------------------------------------------------------ ordered group-by (to host)
@@ -981,6 +988,9 @@ bool host_pinned_ptr(const void *p) {
 // placement, and most of the transfer hidden.  NUT_ERR_UNSUPPORTED: not this shape, or the
 // keys' spread or a partition overflowed the capped layout — the caller takes the hashed
 // path (the host arrays may hold partial output then; it rewrites them).
+// What the host decides (range, admission, heavy keys, sizes, regions, chunks) is
+// go_plan.hpp's; here are the phases that run it: go_sample .. go_fold_heavy over one
+// GoState, listed by groupby_ordered below.
 
 // fold_sorted_groups (fold.hpp): its kinds are the tables' AggKind values
 static_assert(fold::kSumF64 == AK_SUM_F64 && fold::kMinF64 == AK_MIN_F64 && fold::kMaxF64 == AK_MAX_F64 &&
@@ -988,475 +998,88 @@ static_assert(fold::kSumF64 == AK_SUM_F64 && fold::kMinF64 == AK_MIN_F64 && fold
               "fold.hpp kinds");
 using fold::fold_sorted_groups;
 
-nut_status groupby_ordered(nut_ctx *c, const nut_agg_spec *s, uint64_t group_hint, int64_t *keys_h, uint64_t *aggs_h,
-                           uint64_t cap, uint64_t *n_out) {
-  const uint64_t n = s->n;
-  const int na = s->naggs;
-  bool shape = s->nkeys == 1 && !s->prog_mode && s->npred == 0 && !s->key_prog[0].n && c->opt[NUT_OPT_GB_ORDERED] != 0 &&
-               c->opt[NUT_OPT_GB_DIRECT] != 0 && c->opt[NUT_OPT_GB_OPTIMISTIC] != 0 && c->opt[NUT_OPT_GB_PARTITION] != 0 &&
-               c->opt[NUT_OPT_GB_LEVELS] != 1 && c->opt[NUT_OPT_GB_DENSE] != 0 && na >= 1 && n >= (1ull << 24) &&
-               n >= 4 * group_hint && host_pinned_ptr(keys_h) && host_pinned_ptr(aggs_h) && cap > 0;
-  for (int a = 0; a < na && shape; ++a) shape = s->agg_op[a] == NUT_AGG_COUNT || s->agg_expr[a] == NUT_EX_COL;
-  // the 2^14 range cells split into a level-0 and a level-1 digit (NUT_OPT_GB_L0_BITS 6..8;
-  // default 7 + 7: level 0's runs twice as long as at 8 + 6 for level 1's half as long —
-  // same-box A/B at G = 1e7, 1e9 rows, three rounds: step 21.63-21.81 ms vs 22.44-22.56
-  // (8 + 6) and 22.48-22.56 (6 + 8), profiles/r04/groupby1e7/ab_l0bits.txt)
-  const int bits0 = c->opt[NUT_OPT_GB_L0_BITS] >= 6 && c->opt[NUT_OPT_GB_L0_BITS] <= 8 ? (int)c->opt[NUT_OPT_GB_L0_BITS] : 7;
-  const int bits1 = 14 - bits0;
-  const double lam = (double)group_hint / (double)(1 << (bits0 + bits1));
-  c->gb_overflow_rows = 0;
-  c->gb_decline = 0;
-  c->gb_heavy_keys = 0;
-  c->gb_heavy_rows = 0;
-  // every NUT_ERR_UNSUPPORTED names its reason (nut_ctx_groupby_overflow): the caller then
-  // runs the hashed path, with the same result
-  auto decline = [c](uint32_t why) {
-    c->gb_decline = why;
-    return NUT_ERR_UNSUPPORTED;
-  };
-  if (!shape || lam < 100 || ((uintptr_t)s->keys[0] & 15)) return decline(NUT_GB_DECLINE_SHAPE);
-  hipStream_t st = c->stream;
-  // ---- the key range from a strided sample (+ 1/1024 of the span on either side)
-  constexpr uint32_t kSample = 65536;
-  nut_status e = c->misc.reserve(kSample * 8);
-  if (e) return e;
-  hipLaunchKernelGGL(go_sample_kernel, dim3(64), dim3(256), 0, st, s->keys[0], n, kSample, (int64_t *)c->misc.ptr);
-  NUT_HIP(hipGetLastError());
-  std::vector<int64_t> smp(kSample);
-  NUT_HIP(hipMemcpyAsync(smp.data(), c->misc.ptr, kSample * 8, hipMemcpyDeviceToHost, st));
-  NUT_HIP(hipStreamSynchronize(st));
-  const auto mm2 = std::minmax_element(smp.begin(), smp.end());
-  uint64_t lo = (uint64_t)*mm2.first ^ 0x8000000000000000ull, hi = (uint64_t)*mm2.second ^ 0x8000000000000000ull;
-  const uint64_t margin = (hi - lo) >> 10;
-  lo = lo > margin ? lo - margin : 0;
-  hi = hi < ~0ull - margin ? hi + margin : ~0ull;
-  GpRange rg{};
-  rg.lo = lo;
-  rg.span = hi - lo;
-  if (rg.span < (1ull << 16)) return decline(NUT_GB_DECLINE_SHAPE);  // (mul must fit 32 bits; tiny spans hash fine)
-  rg.t = rg.span >> 32 ? 32 - __builtin_clzll(rg.span) : 0;
-  rg.mul = (uint32_t)((1ull << 46) / ((rg.span >> rg.t) + 1));
-  // the sample's keys counted in an open-addressing table (2x the sample): distinct keys
-  // for the admission, repeated ones for the heavy-key split (a sort of the 64 Ki keys took
-  // milliseconds of host time ahead of every call's first kernel)
-  constexpr uint32_t kSlots = 2 * kSample;
-  std::vector<int64_t> tk(kSlots);
-  std::vector<uint32_t> tc(kSlots, 0);
-  for (int64_t k : smp) {
-    uint32_t q = (uint32_t)(mix64((uint64_t)k) >> 32) & (kSlots - 1);
-    while (tc[q] && tk[q] != k) q = (q + 1) & (kSlots - 1);
-    tk[q] = k;
-    ++tc[q];
-  }
-  {  // admission: the sample's distinct keys spread over the level-0 partitions.  Keys
-     // clustered inside the sampled range would overfill some partitions' tables (each
-     // holds ~2x its share of groups) and send the call to the hashed path after all the
-     // work; decline up front instead.  Repeated keys count once: a heavy key is rows,
-     // not groups (the heavy-key split or the overflow arenas below take its rows).
-    const uint32_t np0 = 1u << bits0, bound = 2 * kSample / np0 + 16;
-    std::vector<uint32_t> distinct(np0, 0);
-    for (uint32_t q = 0; q < kSlots; ++q)
-      if (tc[q]) ++distinct[rg.cell((uint64_t)tk[q]) >> bits1];
-    for (uint32_t p = 0; p < np0; ++p)
-      if (distinct[p] > bound) return decline(NUT_GB_DECLINE_CLUSTERED);
-  }
-  // ---- partition buffers: level 0 capped over O (2 x rows per array), level 1 into B2
-  nut_groups *g = new nut_groups();
-  struct Free {
-    nut_groups *g;
-    ~Free() { nut_groups_free(g); }
-  } free_g{g};
-  g->ctx = c;
-  g->nk = 1;
-  g->naggs = na;
-  for (int a = 0; a < na; ++a) g->kinds[a] = kind_of(s, a);
-  int vmap[NUT_MAX_VALS];
-  int nv = 0;
-  for (int j = 0; j < NUT_MAX_VALS; ++j) vmap[j] = -1;
-  for (int a = 0; a < na; ++a)
-    if (s->agg_op[a] != NUT_AGG_COUNT && vmap[s->agg_arg[a][0]] < 0) vmap[s->agg_arg[a][0]] = nv++;
-  const int narr = 3 + nv, nstore = narr - 2;
-  const uint64_t rows = (n + 2 * 65536 + 64 + 31) & ~31ull;
-  // ---- heavy keys (heavy.hpp): a key the sample saw >= 3 times (expected rows >= ~1/22000
-  // of the rows, most of a level-1 partition's share; a key of twice that share is still
-  // sampled < 3 times one time in ten) would overflow its partition.  When such keys
-  // hold >= 5 % of the sample, the <= HK_MAX most frequent are aggregated in one streaming
-  // pass and the other rows, compacted into B2, are what the levels partition.
-  std::vector<int64_t> hkeys;
-  std::vector<uint16_t> hslot;
-  uint64_t hseed1 = 0, hseed2 = 0;
-  if (c->opt[NUT_OPT_GB_HEAVY] != 0) {
-    std::vector<std::pair<uint32_t, int64_t>> cand;  // (sample count, key)
-    for (uint32_t q = 0; q < kSlots; ++q)
-      if (tc[q] >= 3) cand.emplace_back(tc[q], tk[q]);
-    std::sort(cand.begin(), cand.end(), [](const auto &x, const auto &y) {
-      return x.first > y.first || (x.first == y.first && x.second < y.second);
-    });
-    const size_t hmax = std::min<size_t>(HK_MAX, HK_WORDS / na);
-    if (cand.size() > hmax) cand.resize(hmax);
-    uint64_t cover = 0;
-    for (const auto &x : cand) cover += x.first;
-    if (cover * 20 >= kSample) {
-      for (const auto &x : cand) hkeys.push_back(x.second);
-      std::sort(hkeys.begin(), hkeys.end());
-      // the pass's lookup table: a cuckoo table (two slots per key) built here, so every
-      // lookup is two reads; new seeds if a key finds no place (at load <= 1/4, rare)
-      hslot.assign(HK_SLOTS, 0);
-      bool placed = false;
-      for (uint64_t attempt = 0; attempt < 8 && !placed; ++attempt) {
-        hseed1 = mix64(0x9E3779B97F4A7C15ull + 2 * attempt);
-        hseed2 = mix64(0x9E3779B97F4A7C15ull + 2 * attempt + 1);
-        placed = hk_cuckoo(hkeys.data(), (uint32_t)hkeys.size(), hseed1, hseed2, hslot.data());
-      }
-      if (!placed) hkeys.clear();  // (the overflow arenas take them)
-    }
-  }
-  // Exact layout (heavy keys split off): the data is skewed below the heavy keys too
-  // (Zipf-like: keys of ~1/2 to 2 partition shares remain), so the heavy pass's kept rows are
-  // counted per range cell (go_cell_hist_kernel, 8 B per kept row) and both levels' regions
-  // are laid out from the counts — no overflow, no arenas, no arena group-by or host fold.
-  // NUT_OPT_GB_HEAVY = 2 keeps the capped layout behind the heavy pass (A/B, tests).
-  const bool exact = !hkeys.empty() && c->opt[NUT_OPT_GB_HEAVY] != 2;
-  // capped level-1 regions: the even share x slack1 (six standard deviations of a Poisson
-  // count of lambda keys per partition); behind the heavy pass 2.5 x (1e9-row Zipf G = 1e7:
-  // 62 M arena rows at 1.24 x)
-  const double slack1 = exact ? 1.0 : hkeys.empty() ? 1.0 + 6.0 / sqrt(lam) : 2.5;
-  // B2: the level-1 regions (n x slack1 + per-region slack), then level 1's overflow arena
-  // (n / 2 rows, n / 4 with the wider regions, none exact), then one tile of scratch for
-  // runs an exhausted arena cannot take
-  const uint64_t arena1 = ((exact ? 0 : hkeys.empty() ? n / 2 : n / 4) + 31) & ~31ull;
-  const uint64_t b2rows =
-      ((uint64_t)ceil(n * slack1) + (66ull << (bits0 + bits1)) + arena1 + 2 * GP_TILE + 64 + 31) & ~31ull;
-  // (no growth margin; buffers that do not fit send the call to the hashed path, which
-  // needs less)
-  e = c->gp_data.reserve((2 * (size_t)nstore * rows + (size_t)nstore * b2rows) * 8 + 256, false);
-  if (e) {
-    (void)hipGetLastError();
-    return decline(NUT_GB_DECLINE_CAPACITY);
-  }
-  uint64_t *O[GP_MAX_ARR] = {}, *B2[GP_MAX_ARR] = {};
-  for (int i = 1, k = 0; i < narr; ++i) {
-    if (i == 2) continue;
-    O[i] = (uint64_t *)c->gp_data.ptr + (size_t)k * 2 * rows;
-    B2[i] = (uint64_t *)c->gp_data.ptr + 2 * (size_t)nstore * rows + (size_t)k * b2rows;
-    ++k;
-  }
-  const uint64_t *src[GP_MAX_ARR] = {};
-  src[1] = (const uint64_t *)s->keys[0];
-  for (int j = 0; j < NUT_MAX_VALS; ++j)
-    if (vmap[j] >= 0) src[3 + vmap[j]] = (const uint64_t *)s->val_col[j];
-  GpMeta mm{c};
-  c->gb_path = NUT_GB_PARTITIONED_ORDERED;
-  c->gb_levels = 2;
-  c->gb_optimistic = 2;
-  // overflow arenas (a run past its capped region keeps its rows there, gpart.hpp), one
-  // cursor per level: [0] level 0's (in O), [1] level 1's (in B2)
-  unsigned long long *darena = nullptr;
-  NUT_HIP(hipMallocAsync((void **)&darena, 16, st));
-  struct FreeArena {
-    unsigned long long *p;
-    hipStream_t s;
-    ~FreeArena() { (void)hipFreeAsync(p, s); }
-  } free_arena{darena, st};
-  NUT_HIP(hipMemsetAsync(darena, 0, 16, st));
-  uint64_t n0 = n;  // the rows the partition levels read
-  std::vector<uint64_t> hcount;  // heavy pass: the rows each workgroup kept, at hchunk-row strides of B2
-  uint64_t hchunk = 0;
-  unsigned long long *dheavy = nullptr;
-  struct FreeHeavy {
-    unsigned long long *p = nullptr;
-    hipStream_t s;
-    ~FreeHeavy() {
-      if (p) (void)hipFreeAsync(p, s);
-    }
-  } free_heavy{nullptr, st};
-  const uint32_t nh = (uint32_t)hkeys.size();
-  std::vector<uint64_t> cells;  // exact: kept rows per range cell
-  if (nh) {
-    using HK = void (*)(HkArgs);
-    static const HK hkern[NUT_MAX_VALS + 1] = {hk_split_kernel<0>, hk_split_kernel<1>, hk_split_kernel<2>,
-                                               hk_split_kernel<3>, hk_split_kernel<4>};
-    static_assert(NUT_MAX_VALS == 4, "one heavy-pass kernel per value-array count");
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hkern[nv], HK_THREADS, 0) != hipSuccess || per_cu < 1)
-      per_cu = 1;
-    const uint64_t ntiles = (n + HK_TILE - 1) / HK_TILE;
-    const uint64_t hgrid = std::min<uint64_t>(ntiles, (uint64_t)c->num_cus * per_cu);
-    const uint64_t chunk = (ntiles + hgrid - 1) / hgrid;
-    if (chunk * HK_TILE * 8 >= (1ull << 32)) return decline(NUT_GB_DECLINE_CAPACITY);  // (a chunk's buffer resource)
-    // [keys (h), aggregates (h x na), kept rows per workgroup (hgrid), cuckoo slots, exact:
-    // kept rows per range cell]
-    const size_t slot0 = nh + (size_t)nh * na + hgrid, cell0 = slot0 + HK_SLOTS / 4;
-    std::vector<uint64_t> init(cell0 + (exact ? GO_CELLS : 0), 0);
-    memcpy(&init[0], hkeys.data(), (size_t)nh * 8);
-    memcpy(&init[slot0], hslot.data(), HK_SLOTS * 2);
-    for (uint32_t j = 0; j < nh; ++j)
-      for (int a = 0; a < na; ++a) init[nh + (size_t)j * na + a] = agg_init(g->kinds[a]);
-    NUT_HIP(hipMallocAsync((void **)&dheavy, init.size() * 8, st));
-    free_heavy.p = dheavy;
-    NUT_HIP(hipMemcpyAsync(dheavy, init.data(), init.size() * 8, hipMemcpyHostToDevice, st));
-    HkArgs ha{};
-    ha.key = src[1];
-    ha.okey = B2[1];
-    ha.nv = nv;
-    for (int j = 0; j < NUT_MAX_VALS; ++j)
-      if (vmap[j] >= 0) {
-        ha.val[vmap[j]] = src[3 + vmap[j]];
-        ha.oval[vmap[j]] = B2[3 + vmap[j]];
-      }
-    ha.n = n;
-    ha.na = na;
-    for (int a = 0; a < na; ++a) {
-      ha.kind[a] = g->kinds[a];
-      ha.arg[a] = s->agg_op[a] == NUT_AGG_COUNT ? 0 : vmap[s->agg_arg[a][0]];
-    }
-    ha.hk = (const int64_t *)dheavy;
-    ha.slot = (const uint16_t *)((uint64_t *)dheavy + slot0);
-    ha.seed1 = hseed1;
-    ha.seed2 = hseed2;
-    ha.h = nh;
-    ha.hagg = (uint64_t *)dheavy + nh;
-    ha.count = (uint64_t *)dheavy + nh + (size_t)nh * na;
-    ha.chunk = chunk;
-    c->timer.begin(st, NUT_KERNEL_AGGREGATE);
-    hipLaunchKernelGGL(hkern[nv], dim3((unsigned)hgrid), dim3(HK_THREADS), 0, st, ha);
-    if (exact)
-      hipLaunchKernelGGL(go_cell_hist_kernel, dim3((unsigned)hgrid), dim3(GO_HIST_THREADS), 0, st, ha.okey,
-                         (const uint64_t *)ha.count, chunk * HK_TILE, rg, (unsigned long long *)dheavy + cell0);
-    c->timer.end(st);
-    NUT_HIP(hipGetLastError());
-    hcount.resize(hgrid);
-    NUT_HIP(hipMemcpyAsync(hcount.data(), ha.count, hgrid * 8, hipMemcpyDeviceToHost, st));
-    if (exact) {
-      cells.resize(GO_CELLS);
-      NUT_HIP(hipMemcpyAsync(cells.data(), dheavy + cell0, GO_CELLS * 8, hipMemcpyDeviceToHost, st));
-    }
-    NUT_HIP(hipStreamSynchronize(st));
-    hchunk = chunk * HK_TILE;
-    n0 = 0;
-    for (uint64_t x : hcount) n0 += x;
-    src[1] = B2[1];
-    for (int j = 0; j < NUT_MAX_VALS; ++j)
-      if (vmap[j] >= 0) src[3 + vmap[j]] = B2[3 + vmap[j]];
-  }
-  c->gb_heavy_keys = nh;
-  c->gb_heavy_rows = n - n0;
-  if (nh && n0 == 0) {
-    // every row was a heavy key's (few distinct keys under a large group_hint): no row is
-    // left for the partition levels, and the heavy pass's groups are the whole result
-    // (hkeys ascending, every one seen in the data; f64 MIN / MAX back from the table order)
-    std::vector<uint64_t> hw((size_t)nh * na);
-    NUT_HIP(hipMemcpyAsync(hw.data(), dheavy + nh, hw.size() * 8, hipMemcpyDeviceToHost, st));
-    NUT_HIP(hipStreamSynchronize(st));
-    for (uint32_t j = 0; j < nh; ++j)
-      for (int a = 0; a < na; ++a) {
-        uint64_t &x = hw[(size_t)j * na + a];
-        if (g->kinds[a] == AK_MIN_F64 || g->kinds[a] == AK_MAX_F64) x = ord_to_f64(x);
-      }
-    bool over = false;
-    *n_out = fold_sorted_groups(keys_h, aggs_h, 0, cap, hkeys, hw, g->kinds, na, &over);
-    if (over) return fail(NUT_ERR_CAPACITY, "nut_groupby_to_host: capacity " + std::to_string(cap) + " < " +
-                                                std::to_string(nh) + " groups");
+// a stream-ordered allocation, freed on its stream
+struct StreamMem {
+  void *p = nullptr;
+  hipStream_t s = nullptr;
+  nut_status alloc(size_t bytes, hipStream_t st) {
+    s = st;
+    NUT_HIP(hipMallocAsync(&p, bytes, st));
     return NUT_OK;
   }
-  // ---- level 0 (range digit = cell >> bits1): 1.5 x the even share per partition, the rest
-  // of O (~n / 2 rows) its arena
-  const uint64_t ocap = ((3 * rows / 2) >> bits0) & ~1ull;
-  const uint64_t abase0 = ocap << bits0, acap0 = 2 * rows - abase0 - 2 * GP_TILE;
-  std::vector<GpSeg> segs;
-  if (hcount.empty()) {
-    segs.push_back(GpSeg{0, n, 0, 0});
-  } else {  // the heavy pass's per-workgroup runs, gathered into one set of regions
-    for (size_t b = 0; b < hcount.size(); ++b)
-      if (hcount[b]) segs.push_back(GpSeg{b * hchunk, hcount[b], 0, 0});
-    if (segs.empty()) segs.push_back(GpSeg{0, 0, 0, 0});
+  ~StreamMem() {
+    if (p) (void)hipFreeAsync(p, s);
   }
-  for (GpSeg &sg : segs) sg.ocap = ocap;
-  std::vector<uint64_t> hist, p0;
-  std::vector<uint32_t> dig0;  // the level-0 digit of each non-empty level-0 partition
-  const uint32_t nb0 = 1u << bits0, nb1 = 1u << bits1;
-  // exact: level 0 is launched after the metadata upload below (its layout is known now)
-  std::vector<uint32_t> ts0;
-  std::vector<uint64_t> cur0;
-  if (!exact) {
-    c->timer.begin(st, NUT_KERNEL_AGGREGATE);
-    e = gp_level(c, mm, segs, bits1, src, O, narr, hcount.size() > 0, false, hist, &p0, 0, abase0, bits0, &rg, darena,
-                 acap0);
-    c->timer.end(st);
-    if (e) return e == NUT_ERR_CAPACITY ? decline(NUT_GB_DECLINE_ARENA) : e;
-    for (size_t i = 0; i < p0.size(); i += 2) dig0.push_back((uint32_t)(p0[i] / ocap));
-  } else {
-    // digit d's rows start at a 32-row boundary of O after digit d - 1's (256-B aligned)
-    cur0.assign(nb0 + 1, 0);  // + the (unused) overflow flag
-    uint64_t at = 0;
-    for (uint32_t d = 0; d < nb0; ++d) {
-      uint64_t cnt = 0;
-      for (uint32_t q = 0; q < nb1; ++q) cnt += cells[(d << bits1) | q];
-      cur0[d] = at;
-      if (cnt) {
-        p0.push_back(at);
-        p0.push_back(at + cnt);
-        dig0.push_back(d);
-      }
-      at = (at + cnt + 31) & ~31ull;
-    }
-    if (at + 2 * GP_TILE > 2 * rows) return decline(NUT_GB_DECLINE_CAPACITY);
-    for (GpSeg &sg : segs) sg.ocap = 0;
-    gp_tiles(segs, 2 * GP_TILE, ts0);
-  }
-  // ---- level-1 regions, as the hashed path sizes them (capped), or from the cell counts
-  const uint32_t np0 = (uint32_t)(p0.size() / 2);
-  std::vector<GpSeg> s2;
-  uint64_t ovf1 = 0;
-  for (uint32_t i = 0; i < np0; ++i) {
-    GpSeg sg{p0[2 * i], p0[2 * i + 1] - p0[2 * i], 0, 0};
-    sg.obase = ovf1;
-    if (exact) {
-      sg.ocap = 0;
-      for (uint32_t q = 0; q < nb1; ++q) ovf1 += (cells[(dig0[i] << bits1) | q] + 1) & ~1ull;
-    } else {
-      sg.ocap = ((uint64_t)ceil((double)sg.count / nb1 * slack1) + 64 + 1) & ~1ull;
-      ovf1 += sg.ocap << bits1;
-    }
-    s2.push_back(sg);
-  }
-  if (ovf1 + 2 * GP_TILE > b2rows) return decline(NUT_GB_DECLINE_CAPACITY);
-  const uint64_t acap1 = b2rows - ovf1 - 2 * GP_TILE;  // level 1's arena: rows [ovf1, ovf1 + acap1) of B2
-  const uint64_t nparts = (uint64_t)np0 * nb1;
-  if (nparts == 0) return decline(NUT_GB_DECLINE_CAPACITY);  // (no kept row reached level 0: not reached)
-  // chunks of level-0 partitions (in key order) shrinking — 3/8, 1/4, 3/16, 1/16, 1/16,
-  // 1/16: a chunk's transfer (~0.4x its compute) hides behind the next, smaller chunk, and
-  // only the last 1/16 crosses after the work; each launch costs a tail, so few chunks.
-  // The first chunk at 3/8 instead of 1/2 starts the transfers earlier: same-box A/Bs on two
-  // boxes, Zipf-like keys 17.88-17.90 vs 18.33-18.76 and 18.37-18.58 vs 19.12-19.22 ms,
-  // uniform 18.21-18.24 vs 18.34-18.62 and 20.75-21.16 vs 20.90; three 1/16 chunks at the
-  // end instead of 1/8 + 1/16, a third box: Zipf-like 18.42-18.56 vs 19.43-19.59, uniform
-  // 20.18 vs 20.18-20.23 (profiles/r06/groupby1e7/ab_chunks.txt)
-  std::vector<uint32_t> cb{0};
-  for (uint32_t f : {6u, 10u, 13u, 14u, 15u, 16u}) {
-    const uint32_t e1 = (uint32_t)((uint64_t)np0 * f / 16);
-    if (e1 > cb.back()) cb.push_back(e1);
-  }
-  const uint32_t nch = (uint32_t)cb.size() - 1;
-  const int l1_threads = c->opt[NUT_OPT_GB_L1_THREADS] == 512 ? 512 : 1024;  // level 1's scatter workgroup
-  std::vector<uint32_t> tiles, tile0(nch + 1, 0), ntile(nch, 0);
-  for (uint32_t j = 0; j < nch; ++j) {
-    std::vector<GpSeg> sub(s2.begin() + cb[j], s2.begin() + cb[j + 1]);
-    std::vector<uint32_t> ts;
-    ntile[j] = gp_tiles(sub, (uint32_t)l1_threads * GP_ITEMS, ts);
-    for (uint32_t i = 0; i < sub.size(); ++i) s2[cb[j] + i].tile0 = sub[i].tile0;
-    tile0[j] = (uint32_t)tiles.size();
-    tiles.insert(tiles.end(), ts.begin(), ts.end());
-  }
-  std::vector<uint64_t> init(nparts + nch, 0), rend(nparts);  // + one overflow flag per chunk
-  for (uint32_t i = 0; i < np0; ++i) {
-    uint64_t at = s2[i].obase;  // (exact: digit d's rows after digit d - 1's, even starts)
-    for (uint32_t d = 0; d < nb1; ++d) {
-      const uint64_t q = (uint64_t)i * nb1 + d;
-      if (exact) {
-        const uint64_t cnt = cells[(dig0[i] << bits1) | d];
-        init[q] = at;
-        rend[q] = at + cnt;
-        at += (cnt + 1) & ~1ull;
-      } else {
-        init[q] = s2[i].obase + (uint64_t)d * s2[i].ocap;
-        rend[q] = s2[i].obase + (uint64_t)(d + 1) * s2[i].ocap;
-      }
-    }
-  }
-  // the aggregation's table regions: every one holds a full block table (+ the special key)
-  nut_agg_spec s3;
-  memset(&s3, 0, sizeof(s3));
-  s3.n = n;
-  s3.nkeys = 1;
-  s3.keys[0] = (const int64_t *)B2[1];
-  s3.nvals = nv;
-  s3.naggs = na;
-  for (int j = 0; j < NUT_MAX_VALS; ++j)
-    if (vmap[j] >= 0) {
-      s3.val_col[vmap[j]] = B2[3 + vmap[j]];
-      s3.val_type[vmap[j]] = s->val_type[j];
-    }
-  for (int a = 0; a < na; ++a) {
-    s3.agg_op[a] = s->agg_op[a];
-    s3.agg_expr[a] = NUT_EX_COL;
-    if (s->agg_op[a] != NUT_AGG_COUNT) s3.agg_arg[a][0] = vmap[s->agg_arg[a][0]];
-  }
-  const uint64_t per = std::max<uint64_t>(64, 2 * ((group_hint + nparts - 1) / nparts));
-  const uint32_t lcap = agg_lcap(c, 1, na, per, true);
-  if (!lcap) return decline(NUT_GB_DECLINE_CAPACITY);
-  const uint64_t dregion = (uint64_t)lcap + 1;
-  if (dregion > 4097) return decline(NUT_GB_DECLINE_CAPACITY);  // (the ordering pass holds a region in LDS, <= 17 keys per thread)
-  e = alloc_stage(g, nparts * dregion);
-  if (e) return e;
+};
+
+// One call's state: the plan (go_plan.hpp), the buffers and the streams.  The members are
+// destroyed last to first: `drain` (the last one) before every buffer is released.
+struct GoState {
+  nut_ctx *c;
+  const nut_agg_spec *s;
+  uint64_t group_hint;
+  int64_t *keys_h;
+  uint64_t *aggs_h;
+  uint64_t cap;
+  hipStream_t st;
+  uint64_t n;
+  int na, bits0, bits1;
+  double lam;
+  // ---- the plan
+  std::vector<int64_t> smp;
+  GpRange rg{};
+  GoSample tab;
+  GoHeavy hv;
+  uint32_t nh = 0;  // heavy keys
+  GoSizes sz{};
+  GoLevel0 l0;
+  GoLevel1 l1;
+  StagedCols sc;
+  int narr = 0;
+  int l1_threads = 1024;  // level 1's scatter workgroup
+  nut_agg_spec s3;        // the aggregation of B2's arrays
+  uint64_t per = 0, dregion = 0;
+  // ---- the heavy pass's results
+  uint64_t n0 = 0;  // the rows the partition levels read
+  std::vector<uint64_t> hcount;  // heavy pass: the rows each workgroup kept, at hchunk-row strides of B2
+  uint64_t hchunk = 0;
+  std::vector<uint64_t> cells;  // exact: kept rows per range cell
+  // ---- buffers
+  std::unique_ptr<nut_groups, void (*)(nut_groups *)> g{nullptr, nut_groups_free};
+  uint64_t *O[GP_MAX_ARR] = {}, *B2[GP_MAX_ARR] = {};
+  GpMeta mm;
+  // overflow arenas (a run past its capped region keeps its rows there, gpart.hpp), one
+  // cursor per level: [0] level 0's (in O), [1] level 1's (in B2)
+  StreamMem arena;
+  StreamMem heavy;
+  unsigned long long *darena() const { return (unsigned long long *)arena.p; }
+  unsigned long long *dheavy() const { return (unsigned long long *)heavy.p; }
   // device tables, uploaded once
-  GpSeg *dseg;
-  uint32_t *dts;
-  uint64_t *dinit, *drend;
-  // each heavy key's partition (heavy pass): level-0 digit -> its index among the non-empty
-  // level-0 partitions (region d starts at row d * ocap), then the level-1 digit; -1: its
-  // level-0 partition holds no rows (the host folds that key's group)
-  std::vector<int64_t> hq(nh, -1);
-  if (nh) {
-    std::vector<int64_t> idx0((size_t)1 << bits0, -1);
-    for (uint32_t i = 0; i < np0; ++i) idx0[dig0[i]] = i;
-    for (uint32_t j = 0; j < nh; ++j) {
-      const uint32_t cell = rg.cell((uint64_t)hkeys[j]);
-      const int64_t i0 = idx0[cell >> bits1];
-      if (i0 >= 0) hq[j] = i0 * nb1 + (cell & (nb1 - 1));
-    }
-  }
-  e = mm.begin(GpMeta::al(s2.size() * sizeof(GpSeg)) + GpMeta::al(tiles.size() * 4 + 1) + GpMeta::al(init.size() * 8) +
-               2 * GpMeta::al(init.size() * 8) + 4 * GpMeta::al(nparts * 8) + GpMeta::al(64) +
-               2 * GpMeta::al((size_t)nh * 8 + 1) +
-               (exact ? GpMeta::al(segs.size() * sizeof(GpSeg)) + GpMeta::al(ts0.size() * 4 + 1) +
-                            GpMeta::al(cur0.size() * 8)
-                      : 0));
-  if (e) return e;
-  if ((e = mm.up(s2, &dseg)) || (e = mm.up(tiles, &dts)) || (e = mm.up(init, &dinit)) || (e = mm.up(rend, &drend)))
-    return e;
-  if (exact) {  // ---- level 0 into the exact regions (no overflow check: ovf = 0)
-    GpSeg *dseg0;
-    uint32_t *dts0;
-    uint64_t *dcur0;
-    if ((e = mm.up(segs, &dseg0)) || (e = mm.up(ts0, &dts0)) || (e = mm.up(cur0, &dcur0))) return e;
-    GpArrays a0;
-    for (int a = 0; a < GP_MAX_ARR; ++a) {
-      a0.src[a] = src[a];
-      a0.dst[a] = O[a];
-    }
-    a0.narr = narr;
-    c->timer.begin(st, NUT_KERNEL_AGGREGATE);
-    gp_capped_launch(c, a0, dseg0, dts0, (uint32_t)ts0.size(), bits1, (unsigned long long *)dcur0, 0, 0,
-                     (unsigned long long *)dcur0 + nb0, bits0, false, &rg, nullptr, 0, nullptr, 1);
-    c->timer.end(st);
-    NUT_HIP(hipGetLastError());
-  }
+  GpSeg *dseg = nullptr;
+  uint32_t *dts = nullptr;
+  uint64_t *dinit = nullptr, *drend = nullptr, *dmiss = nullptr, *doffs = nullptr;
   int64_t *dhq = nullptr;
-  if ((e = mm.up(hq, &dhq))) return e;
-  uint64_t *dmiss = (uint64_t *)mm.alloc((size_t)nh * 8 + 1);  // heavy keys whose partition's region was full
-  if (nh) NUT_HIP(hipMemsetAsync(dmiss, 0, (size_t)nh * 8, st));
-  unsigned long long *dcur = (unsigned long long *)mm.alloc(init.size() * 8);
-  unsigned long long *dcount = (unsigned long long *)mm.alloc(nparts * 8);
-  uint64_t *doffs = (uint64_t *)mm.alloc(nparts * 8);
-  unsigned long long *drun = (unsigned long long *)mm.alloc(64);
-  // the first overflowing run's start per partition (gp_scatter_kernel's acut), from the
-  // region ends: the aggregation ends each partition there (AggArgs::seg_cut)
-  unsigned long long *dcut = (unsigned long long *)mm.alloc(nparts * 8);
-  NUT_HIP(hipMemcpyAsync(dcut, drend, nparts * 8, hipMemcpyDeviceToDevice, st));
-  NUT_HIP(hipMemcpyAsync(dcur, dinit, init.size() * 8, hipMemcpyDeviceToDevice, st));
-  NUT_HIP(hipMemsetAsync(drun, 0, 64, st));
+  unsigned long long *dcur = nullptr, *dcount = nullptr, *drun = nullptr, *dcut = nullptr;
+  GpArrays ar;  // level 1: O -> B2
   // the ordered result on the device (at most one group per row, at most cap)
-  const uint64_t rcap = std::min<uint64_t>(cap, n);
-  if (!c->copy_stream) NUT_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  uint64_t rcap = 0;
+  int64_t *rk = nullptr;
+  uint64_t *ra = nullptr;
+  volatile uint64_t *runs = nullptr;  // [nch] (pinned: 512 words)
+  uint64_t used0 = 0, used1 = 0;      // the arenas' fill
+  std::vector<uint64_t> miss;         // heavy keys whose partition's region was full
+  uint64_t done = 0;                  // groups already sent to the host
+  bool over = false;
   // released on every return, after the copy stream has drained (it reads `res` and
   // waits on the events)
-  struct Cleanup {
+  struct Drain {
     nut_ctx *c;
     hipStream_t st;
-    uint64_t *res = nullptr;
+    bool armed = false;
+    StreamMem res;
     std::vector<hipEvent_t> ev, ev1, eva;
-    ~Cleanup() {
+    ~Drain() {
+      if (!armed) return;
       if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
       if (c->order_stream) (void)hipStreamSynchronize(c->order_stream);
       (void)hipStreamSynchronize(c->copy_stream);
@@ -1464,24 +1087,277 @@ nut_status groupby_ordered(nut_ctx *c, const nut_agg_spec *s, uint64_t group_hin
         for (auto x : *v)
           if (x) (void)hipEventDestroy(x);
       c->stream = st;
-      if (res) (void)hipFreeAsync(res, st);
     }
-  } cl{c, st};
-  NUT_HIP(hipMallocAsync((void **)&cl.res, rcap * 8 * (1 + (size_t)na), st));
-  int64_t *rk = (int64_t *)cl.res;
-  uint64_t *ra = cl.res + rcap;
-  std::vector<hipEvent_t> &ev = cl.ev;
-  ev.assign(nch, nullptr);
-  for (auto &x : ev) NUT_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-  volatile uint64_t *runs = (volatile uint64_t *)c->host_pinned + 64;  // [nch] (pinned: 512 words)
-  NUT_HIP(hipFuncSetAttribute((const void *)go_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)go_order_lds(dregion)));
-  GpArrays ar;
-  for (int a = 0; a < GP_MAX_ARR; ++a) {
-    ar.src[a] = O[a];
-    ar.dst[a] = B2[a];
+  } drain;
+
+  GoState(nut_ctx *c_, const nut_agg_spec *s_, uint64_t hint, int64_t *kh, uint64_t *ah, uint64_t cap_)
+      : c(c_), s(s_), group_hint(hint), keys_h(kh), aggs_h(ah), cap(cap_), st(c_->stream), n(s_->n), na(s_->naggs),
+        mm{c_}, drain{c_, c_->stream} {}
+  // every NUT_ERR_UNSUPPORTED names its reason (nut_ctx_groupby_overflow): the caller then
+  // runs the hashed path, with the same result
+  nut_status decline(uint32_t why) const {
+    c->gb_decline = why;
+    return NUT_ERR_UNSUPPORTED;
   }
-  ar.narr = narr;
+};
+
+// ---- the key range's strided sample
+nut_status go_sample(GoState &z) {
+  nut_ctx *c = z.c;
+  nut_status e = c->misc.reserve(kGoSample * 8);
+  if (e) return e;
+  hipLaunchKernelGGL(go_sample_kernel, dim3(64), dim3(256), 0, z.st, z.s->keys[0], z.n, kGoSample, (int64_t *)c->misc.ptr);
+  NUT_HIP(hipGetLastError());
+  z.smp.resize(kGoSample);
+  NUT_HIP(hipMemcpyAsync(z.smp.data(), c->misc.ptr, kGoSample * 8, hipMemcpyDeviceToHost, z.st));
+  NUT_HIP(hipStreamSynchronize(z.st));
+  return NUT_OK;
+}
+
+// ---- the plan before the first partition kernel: range, admission, heavy keys, buffers
+nut_status go_plan(GoState &z) {
+  nut_ctx *c = z.c;
+  const auto mm2 = std::minmax_element(z.smp.begin(), z.smp.end());
+  if (uint32_t why = go_range(*mm2.first, *mm2.second, &z.rg)) return z.decline(why);
+  go_sample_table(z.smp, &z.tab);
+  if (uint32_t why = go_admit(z.tab, z.rg, z.bits0)) return z.decline(why);
+  z.g.reset(new nut_groups());
+  nut_groups *g = z.g.get();
+  g->ctx = c;
+  g->nk = 1;
+  g->naggs = z.na;
+  for (int a = 0; a < z.na; ++a) g->kinds[a] = kind_of(z.s, a);
+  z.sc = staged_cols(z.s, 1);
+  z.narr = 3 + z.sc.nv;
+  const int nstore = z.narr - 2;
+  if (c->opt[NUT_OPT_GB_HEAVY] != 0) go_heavy_keys(z.tab, z.na, &z.hv);
+  z.nh = (uint32_t)z.hv.keys.size();
+  z.sz = go_sizes(z.n, z.bits0, nstore, z.lam, z.nh != 0, c->opt[NUT_OPT_GB_HEAVY] == 2);
+  // (no growth margin; buffers that do not fit send the call to the hashed path, which
+  // needs less)
+  if (c->gp_data.reserve(z.sz.data_bytes, false)) {
+    (void)hipGetLastError();
+    return z.decline(NUT_GB_DECLINE_CAPACITY);
+  }
+  for (int i = 1, k = 0; i < z.narr; ++i) {
+    if (i == 2) continue;
+    z.O[i] = (uint64_t *)c->gp_data.ptr + (size_t)k * 2 * z.sz.rows;
+    z.B2[i] = (uint64_t *)c->gp_data.ptr + 2 * (size_t)nstore * z.sz.rows + (size_t)k * z.sz.b2rows;
+    ++k;
+  }
+  c->gb_path = NUT_GB_PARTITIONED_ORDERED;
+  c->gb_levels = 2;
+  c->gb_optimistic = 2;
+  nut_status e = z.arena.alloc(16, z.st);
+  if (e) return e;
+  NUT_HIP(hipMemsetAsync(z.arena.p, 0, 16, z.st));
+  return NUT_OK;
+}
+
+// the heavy pass's arguments: the caller's columns in, B2 out, the tables in z.heavy (slot0:
+// the cuckoo slots' word there)
+HkArgs go_heavy_args(const GoState &z, size_t slot0, uint64_t chunk) {
+  const int na = z.na;
+  const uint32_t nh = z.nh;
+  const int *vmap = z.sc.vmap;
+  uint64_t *dheavy = (uint64_t *)z.heavy.p;
+  HkArgs ha{};
+  ha.key = z.sc.src[1];
+  ha.okey = z.B2[1];
+  ha.nv = z.sc.nv;
+  for (int j = 0; j < NUT_MAX_VALS; ++j)
+    if (vmap[j] >= 0) {
+      ha.val[vmap[j]] = z.sc.src[3 + vmap[j]];
+      ha.oval[vmap[j]] = z.B2[3 + vmap[j]];
+    }
+  ha.n = z.n;
+  ha.na = na;
+  for (int a = 0; a < na; ++a) {
+    ha.kind[a] = z.g->kinds[a];
+    ha.arg[a] = z.s->agg_op[a] == NUT_AGG_COUNT ? 0 : vmap[z.s->agg_arg[a][0]];
+  }
+  ha.hk = (const int64_t *)dheavy;
+  ha.slot = (const uint16_t *)(dheavy + slot0);
+  ha.seed1 = z.hv.seed1;
+  ha.seed2 = z.hv.seed2;
+  ha.h = nh;
+  ha.hagg = dheavy + nh;
+  ha.count = dheavy + nh + (size_t)nh * na;
+  ha.chunk = chunk;
+  return ha;
+}
+
+// ---- the heavy pass (heavy.hpp): the heavy keys' rows aggregated, the others compacted into
+// B2 (which the levels then read), exact: counted per range cell
+nut_status go_heavy_pass(GoState &z) {
+  nut_ctx *c = z.c;
+  hipStream_t st = z.st;
+  const int na = z.na, nv = z.sc.nv;
+  const uint32_t nh = z.nh;
+  const int *vmap = z.sc.vmap;
+  const nut_groups *g = z.g.get();
+  using HK = void (*)(HkArgs);
+  static const HK hkern[NUT_MAX_VALS + 1] = {hk_split_kernel<0>, hk_split_kernel<1>, hk_split_kernel<2>,
+                                             hk_split_kernel<3>, hk_split_kernel<4>};
+  static_assert(NUT_MAX_VALS == 4, "one heavy-pass kernel per value-array count");
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, hkern[nv], HK_THREADS, 0) != hipSuccess || per_cu < 1)
+    per_cu = 1;
+  GoHeavyGrid hg;
+  if (uint32_t why = go_heavy_grid(z.n, c->num_cus, per_cu, &hg)) return z.decline(why);
+  const uint64_t hgrid = hg.hgrid, chunk = hg.chunk;
+  // [keys (h), aggregates (h x na), kept rows per workgroup (hgrid), cuckoo slots, exact:
+  // kept rows per range cell]
+  const size_t slot0 = nh + (size_t)nh * na + hgrid, cell0 = slot0 + HK_SLOTS / 4;
+  std::vector<uint64_t> init(cell0 + (z.sz.exact ? GO_CELLS : 0), 0);
+  memcpy(&init[0], z.hv.keys.data(), (size_t)nh * 8);
+  memcpy(&init[slot0], z.hv.slot.data(), HK_SLOTS * 2);
+  for (uint32_t j = 0; j < nh; ++j)
+    for (int a = 0; a < na; ++a) init[nh + (size_t)j * na + a] = agg_init(g->kinds[a]);
+  nut_status e = z.heavy.alloc(init.size() * 8, st);
+  if (e) return e;
+  unsigned long long *dheavy = z.dheavy();
+  NUT_HIP(hipMemcpyAsync(dheavy, init.data(), init.size() * 8, hipMemcpyHostToDevice, st));
+  const HkArgs ha = go_heavy_args(z, slot0, chunk);
+  c->timer.begin(st, NUT_KERNEL_AGGREGATE);
+  hipLaunchKernelGGL(hkern[nv], dim3((unsigned)hgrid), dim3(HK_THREADS), 0, st, ha);
+  if (z.sz.exact)
+    hipLaunchKernelGGL(go_cell_hist_kernel, dim3((unsigned)hgrid), dim3(GO_HIST_THREADS), 0, st, ha.okey,
+                       (const uint64_t *)ha.count, chunk * HK_TILE, z.rg, (unsigned long long *)dheavy + cell0);
+  c->timer.end(st);
+  NUT_HIP(hipGetLastError());
+  z.hcount.resize(hgrid);
+  NUT_HIP(hipMemcpyAsync(z.hcount.data(), ha.count, hgrid * 8, hipMemcpyDeviceToHost, st));
+  if (z.sz.exact) {
+    z.cells.resize(GO_CELLS);
+    NUT_HIP(hipMemcpyAsync(z.cells.data(), dheavy + cell0, GO_CELLS * 8, hipMemcpyDeviceToHost, st));
+  }
+  NUT_HIP(hipStreamSynchronize(st));
+  z.hchunk = chunk * HK_TILE;
+  z.n0 = 0;
+  for (uint64_t x : z.hcount) z.n0 += x;
+  z.sc.src[1] = z.B2[1];
+  for (int j = 0; j < NUT_MAX_VALS; ++j)
+    if (vmap[j] >= 0) z.sc.src[3 + vmap[j]] = z.B2[3 + vmap[j]];
+  return NUT_OK;
+}
+
+// the heavy keys' aggregate words, as result words (f64 MIN / MAX back from the table order)
+nut_status go_heavy_words(GoState &z, std::vector<uint64_t> &hw) {
+  const int na = z.na;
+  hw.resize((size_t)z.nh * na);
+  NUT_HIP(hipMemcpyAsync(hw.data(), z.dheavy() + z.nh, hw.size() * 8, hipMemcpyDeviceToHost, z.st));
+  NUT_HIP(hipStreamSynchronize(z.st));
+  for (uint32_t j = 0; j < z.nh; ++j)
+    for (int a = 0; a < na; ++a) {
+      uint64_t &x = hw[(size_t)j * na + a];
+      if (z.g->kinds[a] == AK_MIN_F64 || z.g->kinds[a] == AK_MAX_F64) x = ord_to_f64(x);
+    }
+  return NUT_OK;
+}
+
+// ---- level 0 (range digit = cell >> bits1): capped, run here; exact, laid out here and
+// launched after the metadata upload (go_upload)
+nut_status go_level0(GoState &z) {
+  nut_ctx *c = z.c;
+  go_l0_segs(z.n, z.hcount, z.hchunk, z.sz.ocap, &z.l0.segs);
+  if (z.sz.exact) {
+    if (uint32_t why = go_l0_exact(z.cells, z.bits0, z.sz.rows, &z.l0)) return z.decline(why);
+    return NUT_OK;
+  }
+  std::vector<uint64_t> hist;
+  c->timer.begin(z.st, NUT_KERNEL_AGGREGATE);
+  nut_status e = gp_level(c, z.mm, z.l0.segs, z.bits1, z.sc.src, z.O, z.narr, z.hcount.size() > 0, false, hist, &z.l0.p0,
+                          0, z.sz.abase0, z.bits0, &z.rg, z.darena(), z.sz.acap0);
+  c->timer.end(z.st);
+  if (e) return e == NUT_ERR_CAPACITY ? z.decline(NUT_GB_DECLINE_ARENA) : e;
+  go_l0_capped(z.sz.ocap, &z.l0);
+  return NUT_OK;
+}
+
+// ---- level 1's plan, and the aggregation's table regions: every one holds a full block
+// table (+ the special key)
+nut_status go_plan_level1(GoState &z) {
+  nut_ctx *c = z.c;
+  z.l1_threads = c->opt[NUT_OPT_GB_L1_THREADS] == 512 ? 512 : 1024;
+  if (uint32_t why = go_level1(z.l0, z.cells, z.sz.exact, z.bits0, z.sz.slack1, z.sz.b2rows, z.l1_threads, z.rg,
+                               z.hv.keys, &z.l1))
+    return z.decline(why);
+  z.s3 = staged_spec(z.s, z.sc, 1, z.n, z.B2);
+  z.per = std::max<uint64_t>(64, 2 * ((z.group_hint + z.l1.nparts - 1) / z.l1.nparts));
+  const uint32_t lcap = agg_lcap(c, 1, z.na, z.per, true);
+  if (!lcap) return z.decline(NUT_GB_DECLINE_CAPACITY);
+  z.dregion = (uint64_t)lcap + 1;
+  if (z.dregion > 4097) return z.decline(NUT_GB_DECLINE_CAPACITY);  // (the ordering pass holds a region in LDS, <= 17 keys per thread)
+  return alloc_stage(z.g.get(), z.l1.nparts * z.dregion);
+}
+
+// ---- the device tables, uploaded once; exact: level 0 into its regions
+nut_status go_upload(GoState &z) {
+  nut_ctx *c = z.c;
+  hipStream_t st = z.st;
+  GpMeta &mm = z.mm;
+  const GoLevel0 &l0 = z.l0;
+  const GoLevel1 &l1 = z.l1;
+  const uint32_t nh = z.nh, nb0 = 1u << z.bits0;
+  const uint64_t nparts = l1.nparts;
+  const bool exact = z.sz.exact;
+  nut_status e =
+      mm.begin(GpMeta::al(l1.s2.size() * sizeof(GpSeg)) + GpMeta::al(l1.tiles.size() * 4 + 1) +
+               GpMeta::al(l1.init.size() * 8) + 2 * GpMeta::al(l1.init.size() * 8) + 4 * GpMeta::al(nparts * 8) +
+               GpMeta::al(64) + 2 * GpMeta::al((size_t)nh * 8 + 1) +
+               (exact ? GpMeta::al(l0.segs.size() * sizeof(GpSeg)) + GpMeta::al(l0.ts0.size() * 4 + 1) +
+                            GpMeta::al(l0.cur0.size() * 8)
+                      : 0));
+  if (e) return e;
+  if ((e = mm.up(l1.s2, &z.dseg)) || (e = mm.up(l1.tiles, &z.dts)) || (e = mm.up(l1.init, &z.dinit)) ||
+      (e = mm.up(l1.rend, &z.drend)))
+    return e;
+  if (exact) {  // ---- level 0 into the exact regions (no overflow check: ovf = 0)
+    GpSeg *dseg0;
+    uint32_t *dts0;
+    uint64_t *dcur0;
+    if ((e = mm.up(l0.segs, &dseg0)) || (e = mm.up(l0.ts0, &dts0)) || (e = mm.up(l0.cur0, &dcur0))) return e;
+    c->timer.begin(st, NUT_KERNEL_AGGREGATE);
+    gp_capped_launch(c, gp_arrays(z.sc.src, z.O, z.narr), dseg0, dts0, (uint32_t)l0.ts0.size(), z.bits1,
+                     (unsigned long long *)dcur0, 0, 0, (unsigned long long *)dcur0 + nb0, z.bits0, false, &z.rg, nullptr,
+                     0, nullptr, 1);
+    c->timer.end(st);
+    NUT_HIP(hipGetLastError());
+  }
+  if ((e = mm.up(l1.hq, &z.dhq))) return e;
+  z.dmiss = (uint64_t *)mm.alloc((size_t)nh * 8 + 1);  // heavy keys whose partition's region was full
+  if (nh) NUT_HIP(hipMemsetAsync(z.dmiss, 0, (size_t)nh * 8, st));
+  z.dcur = (unsigned long long *)mm.alloc(l1.init.size() * 8);
+  z.dcount = (unsigned long long *)mm.alloc(nparts * 8);
+  z.doffs = (uint64_t *)mm.alloc(nparts * 8);
+  z.drun = (unsigned long long *)mm.alloc(64);
+  // the first overflowing run's start per partition (gp_scatter_kernel's acut), from the
+  // region ends: the aggregation ends each partition there (AggArgs::seg_cut)
+  z.dcut = (unsigned long long *)mm.alloc(nparts * 8);
+  NUT_HIP(hipMemcpyAsync(z.dcut, z.drend, nparts * 8, hipMemcpyDeviceToDevice, st));
+  NUT_HIP(hipMemcpyAsync(z.dcur, z.dinit, l1.init.size() * 8, hipMemcpyDeviceToDevice, st));
+  NUT_HIP(hipMemsetAsync(z.drun, 0, 64, st));
+  return NUT_OK;
+}
+
+// ---- the result buffer, the streams and their events
+nut_status go_streams(GoState &z) {
+  nut_ctx *c = z.c;
+  const uint32_t nch = z.l1.nch();
+  z.rcap = std::min<uint64_t>(z.cap, z.n);
+  if (!c->copy_stream) NUT_HIP(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  z.drain.armed = true;
+  nut_status e = z.drain.res.alloc(z.rcap * 8 * (1 + (size_t)z.na), z.st);
+  if (e) return e;
+  z.rk = (int64_t *)z.drain.res.p;
+  z.ra = (uint64_t *)z.drain.res.p + z.rcap;
+  z.drain.ev.assign(nch, nullptr);
+  for (auto &x : z.drain.ev) NUT_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+  z.runs = (volatile uint64_t *)c->host_pinned + 64;
+  NUT_HIP(hipFuncSetAttribute((const void *)go_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)go_order_lds(z.dregion)));
+  z.ar = gp_arrays(z.O, z.B2, z.narr);
   // Four streams: level 1 of every chunk back to back on the context's stream; each
   // chunk's aggregation on a second one as soon as its level 1 is done (it overlaps the
   // next chunk's level 1, so neither launch's tail idles the chip); its ordering on a third
@@ -1492,161 +1368,218 @@ nut_status groupby_ordered(nut_ctx *c, const nut_agg_spec *s, uint64_t group_hin
   // all three: 20.4 vs 19.3 ms per G = 1e7 step, profiles/r06/groupby1e7/ab_order_priority.txt)
   if (!c->aux_stream) NUT_HIP(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
   if (!c->order_stream) NUT_HIP(hipStreamCreateWithFlags(&c->order_stream, hipStreamNonBlocking));
-  hipStream_t ax = c->aux_stream, ox = c->order_stream;
-  std::vector<hipEvent_t> &ev1 = cl.ev1, &eva = cl.eva;
-  ev1.assign(nch, nullptr);
-  eva.assign(nch, nullptr);
-  for (auto &x : ev1) NUT_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-  for (auto &x : eva) NUT_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-  auto enqueue = [&](uint32_t j) -> nut_status {
-    const uint32_t a0 = cb[j], a1 = cb[j + 1];
-    const uint64_t q0 = (uint64_t)a0 * nb1, nq = (uint64_t)(a1 - a0) * nb1;
-    c->timer.begin(st, NUT_KERNEL_AGGREGATE);
-    gp_capped_launch(c, ar, dseg + a0, dts + tile0[j], ntile[j], 0, dcur + q0, 0, exact ? 0 : ovf1, dcur + nparts + j,
-                     bits1, false, &rg, exact ? nullptr : darena + 1, acap1, exact ? nullptr : dcut + q0, 0,
-                     l1_threads, j ? (int)c->opt[NUT_OPT_GB_L1_SPARE] : 0);
-    c->timer.end(st);
-    NUT_HIP(hipGetLastError());
-    NUT_HIP(hipEventRecord(ev1[j], st));
-    NUT_HIP(hipStreamWaitEvent(ax, ev1[j], 0));
-    // partition rows [first row, cursor after the scatter), cut at the first run that went
-    // to the arena (the rows after it are not the partition's): min(cursor, cut), read by
-    // the aggregation's blocks themselves
-    LaunchExtra sg;
-    sg.seg_off = dinit + q0;
-    sg.seg_end = (const uint64_t *)dcur + q0;
-    sg.seg_cut = (const uint64_t *)dcut + q0;
-    sg.nseg = (uint32_t)nq;
-    sg.dense = true;
-    sg.dcount = dcount + q0;
-    sg.dregion = dregion;
-    sg.dbase = q0;
-    c->stream = ax;  // (launch_agg launches on the context's stream)
-    nut_status e2 = launch_agg(g, &s3, per, g->kinds, &sg);
-    c->stream = st;
-    if (e2) return e2;
-    if (nh)  // the heavy keys' groups of this chunk's partitions join their regions before the ordering
-      hipLaunchKernelGGL(go_heavy_insert_kernel, dim3(1), dim3(1024), 0, ax, (const int64_t *)dheavy,
-                         (const uint64_t *)dheavy + nh, nh, na, (const int64_t *)dhq, q0, nq, dcount, g->gt.slot,
-                         g->gt.agg, g->gt.cap + 1, dregion, dmiss);
-    NUT_HIP(hipEventRecord(eva[j], ax));
-    NUT_HIP(hipStreamWaitEvent(ox, eva[j], 0));
-    c->timer.begin(ox, NUT_KERNEL_AGGREGATE);
-    hipLaunchKernelGGL(go_scan_kernel, dim3(1), dim3(1024), 0, ox, (const unsigned long long *)dcount + q0, (uint32_t)nq,
-                       doffs + q0, drun);
-    hipLaunchKernelGGL(go_order_kernel, dim3((unsigned)nq), dim3(GO_ORDER_THREADS), (unsigned)go_order_lds(dregion), ox,
-                       (const uint64_t *)g->gt.slot, (const uint64_t *)g->gt.agg, g->gt.cap + 1, dregion, q0,
-                       (const unsigned long long *)dcount + q0, (const uint64_t *)doffs + q0, na, g->gt.kinds, rk, ra,
-                       rcap);
-    c->timer.end(ox);
-    NUT_HIP(hipGetLastError());
-    NUT_HIP(hipMemcpyAsync((void *)(runs + j), drun, 8, hipMemcpyDeviceToHost, ox));
-    NUT_HIP(hipEventRecord(ev[j], ox));
-    return NUT_OK;
-  };
-  // every chunk queued (nothing waits for the host); chunk j crosses on the copy stream
-  // once its count is known
-  uint64_t done = 0;  // groups already sent to the host
-  bool over = false;
-  for (uint32_t j = 0; j < nch; ++j)
-    if ((e = enqueue(j))) return e;
+  z.drain.ev1.assign(nch, nullptr);
+  z.drain.eva.assign(nch, nullptr);
+  for (auto &x : z.drain.ev1) NUT_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+  for (auto &x : z.drain.eva) NUT_HIP(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+  return NUT_OK;
+}
+
+// ---- chunk j: level 1, aggregation, the heavy keys' groups, ordering, its running total
+nut_status go_enqueue(GoState &z, uint32_t j) {
+  nut_ctx *c = z.c;
+  hipStream_t st = z.st, ax = c->aux_stream, ox = c->order_stream;
+  const GoLevel1 &l1 = z.l1;
+  nut_groups *g = z.g.get();
+  const bool exact = z.sz.exact;
+  const uint32_t nb1 = 1u << z.bits1, nh = z.nh;
+  const uint64_t nparts = l1.nparts, dregion = z.dregion;
+  const uint32_t a0 = l1.cb[j], a1 = l1.cb[j + 1];
+  const uint64_t q0 = (uint64_t)a0 * nb1, nq = (uint64_t)(a1 - a0) * nb1;
+  c->timer.begin(st, NUT_KERNEL_AGGREGATE);
+  gp_capped_launch(c, z.ar, z.dseg + a0, z.dts + l1.tile0[j], l1.ntile[j], 0, z.dcur + q0, 0, exact ? 0 : l1.ovf1,
+                   z.dcur + nparts + j, z.bits1, false, &z.rg, exact ? nullptr : z.darena() + 1, l1.acap1,
+                   exact ? nullptr : z.dcut + q0, 0, z.l1_threads, j ? (int)c->opt[NUT_OPT_GB_L1_SPARE] : 0);
+  c->timer.end(st);
+  NUT_HIP(hipGetLastError());
+  NUT_HIP(hipEventRecord(z.drain.ev1[j], st));
+  NUT_HIP(hipStreamWaitEvent(ax, z.drain.ev1[j], 0));
+  // partition rows [first row, cursor after the scatter), cut at the first run that went
+  // to the arena (the rows after it are not the partition's): min(cursor, cut), read by
+  // the aggregation's blocks themselves
+  LaunchExtra sg;
+  sg.seg_off = z.dinit + q0;
+  sg.seg_end = (const uint64_t *)z.dcur + q0;
+  sg.seg_cut = (const uint64_t *)z.dcut + q0;
+  sg.nseg = (uint32_t)nq;
+  sg.dense = true;
+  sg.dcount = z.dcount + q0;
+  sg.dregion = dregion;
+  sg.dbase = q0;
+  c->stream = ax;  // (launch_agg launches on the context's stream)
+  nut_status e2 = launch_agg(g, &z.s3, z.per, g->kinds, &sg);
+  c->stream = st;
+  if (e2) return e2;
+  if (nh)  // the heavy keys' groups of this chunk's partitions join their regions before the ordering
+    hipLaunchKernelGGL(go_heavy_insert_kernel, dim3(1), dim3(1024), 0, ax, (const int64_t *)z.dheavy(),
+                       (const uint64_t *)z.dheavy() + nh, nh, z.na, (const int64_t *)z.dhq, q0, nq, z.dcount, g->gt.slot,
+                       g->gt.agg, g->gt.cap + 1, dregion, z.dmiss);
+  NUT_HIP(hipEventRecord(z.drain.eva[j], ax));
+  NUT_HIP(hipStreamWaitEvent(ox, z.drain.eva[j], 0));
+  c->timer.begin(ox, NUT_KERNEL_AGGREGATE);
+  hipLaunchKernelGGL(go_scan_kernel, dim3(1), dim3(1024), 0, ox, (const unsigned long long *)z.dcount + q0, (uint32_t)nq,
+                     z.doffs + q0, z.drun);
+  hipLaunchKernelGGL(go_order_kernel, dim3((unsigned)nq), dim3(GO_ORDER_THREADS), (unsigned)go_order_lds(dregion), ox,
+                     (const uint64_t *)g->gt.slot, (const uint64_t *)g->gt.agg, g->gt.cap + 1, dregion, q0,
+                     (const unsigned long long *)z.dcount + q0, (const uint64_t *)z.doffs + q0, z.na, g->gt.kinds, z.rk,
+                     z.ra, z.rcap);
+  c->timer.end(ox);
+  NUT_HIP(hipGetLastError());
+  NUT_HIP(hipMemcpyAsync((void *)(z.runs + j), z.drun, 8, hipMemcpyDeviceToHost, ox));
+  NUT_HIP(hipEventRecord(z.drain.ev[j], ox));
+  return NUT_OK;
+}
+
+// ---- chunk j crosses on the copy stream once its count is known; then the capped level-1
+// flags (an exhausted arena), the arenas' fill and the aggregation's control words
+nut_status go_drain(GoState &z) {
+  nut_ctx *c = z.c;
+  hipStream_t st = z.st;
+  const int na = z.na;
+  const uint32_t nch = z.l1.nch(), nh = z.nh;
   for (uint32_t j = 0; j < nch; ++j) {
-    NUT_HIP(hipEventSynchronize(ev[j]));
-    const uint64_t total = runs[j];
-    if (total > rcap) over = true;
-    if (!over && total > done) {
-      NUT_HIP(hipStreamWaitEvent(c->copy_stream, ev[j], 0));
-      NUT_HIP(hipMemcpyAsync(keys_h + done, rk + done, (total - done) * 8, hipMemcpyDeviceToHost, c->copy_stream));
-      NUT_HIP(hipMemcpyAsync(aggs_h + done * na, ra + done * na, (total - done) * 8 * na, hipMemcpyDeviceToHost,
+    NUT_HIP(hipEventSynchronize(z.drain.ev[j]));
+    const uint64_t total = z.runs[j], done = z.done;
+    if (total > z.rcap) z.over = true;
+    if (!z.over && total > done) {
+      NUT_HIP(hipStreamWaitEvent(c->copy_stream, z.drain.ev[j], 0));
+      NUT_HIP(hipMemcpyAsync(z.keys_h + done, z.rk + done, (total - done) * 8, hipMemcpyDeviceToHost, c->copy_stream));
+      NUT_HIP(hipMemcpyAsync(z.aggs_h + done * na, z.ra + done * na, (total - done) * 8 * na, hipMemcpyDeviceToHost,
                              c->copy_stream));
     }
-    done = total;
+    z.done = total;
   }
-  // the capped level-1 flags (an exhausted arena), the arenas' fill and the aggregation's
-  // control words
-  NUT_HIP(hipStreamSynchronize(ax));
-  NUT_HIP(hipStreamSynchronize(ox));
+  NUT_HIP(hipStreamSynchronize(c->aux_stream));
+  NUT_HIP(hipStreamSynchronize(c->order_stream));
   // (everything in gp_meta is read now: the arenas' group-by below may partition, and its
   // own tables take gp_meta)
-  std::vector<uint64_t> flags(nch), miss(nh);
-  NUT_HIP(hipMemcpyAsync(flags.data(), dcur + nparts, nch * 8, hipMemcpyDeviceToHost, st));
-  if (nh) NUT_HIP(hipMemcpyAsync(miss.data(), dmiss, (size_t)nh * 8, hipMemcpyDeviceToHost, st));
+  std::vector<uint64_t> flags(nch);
+  z.miss.resize(nh);
+  NUT_HIP(hipMemcpyAsync(flags.data(), z.dcur + z.l1.nparts, nch * 8, hipMemcpyDeviceToHost, st));
+  if (nh) NUT_HIP(hipMemcpyAsync(z.miss.data(), z.dmiss, (size_t)nh * 8, hipMemcpyDeviceToHost, st));
   uint32_t ctl[4];
-  NUT_HIP(hipMemcpyAsync(c->host_pinned, g->gt.ctl, 16, hipMemcpyDeviceToHost, st));
-  NUT_HIP(hipMemcpyAsync(c->host_pinned + 2, darena, 16, hipMemcpyDeviceToHost, st));
+  NUT_HIP(hipMemcpyAsync(c->host_pinned, z.g->gt.ctl, 16, hipMemcpyDeviceToHost, st));
+  NUT_HIP(hipMemcpyAsync(c->host_pinned + 2, z.darena(), 16, hipMemcpyDeviceToHost, st));
   NUT_HIP(hipStreamSynchronize(st));
   memcpy(ctl, c->host_pinned, 16);
-  const uint64_t used0 = c->host_pinned[2], used1 = c->host_pinned[3];
+  z.used0 = c->host_pinned[2];
+  z.used1 = c->host_pinned[3];
   NUT_HIP(hipStreamSynchronize(c->copy_stream));
   for (uint64_t f : flags)
-    if (f) return decline(NUT_GB_DECLINE_ARENA);  // a level-1 run found the arena full
-  if (ctl[1] & 4u) return decline(NUT_GB_DECLINE_TABLE);  // a partition outgrew its block's table
-  c->gb_overflow_rows = used0 + used1;
-  if (used0 + used1 && !over) {
-    // the arenas' rows (heavy keys' excess, mostly) aggregated on their own and folded
-    // into the ordered host result
-    // (copied out of gp_data first — the arenas live there and the group-by may partition,
-    // which takes gp_data — then one group-by over both levels' rows, on whichever path its
-    // size picks)
-    const uint64_t ar_rows = used0 + used1, ar_str = (ar_rows + 31) & ~31ull;  // (arrays 256-B aligned: vector loads)
-    uint64_t *ar = nullptr;
-    NUT_HIP(hipMallocAsync((void **)&ar, ar_str * 8 * (1 + (size_t)nv), st));
-    struct FreeAr {
-      uint64_t *p;
-      hipStream_t s;
-      ~FreeAr() { (void)hipFreeAsync(p, s); }
-    } free_ar{ar, st};
-    for (int i = 1; i < narr; ++i) {
-      if (i == 2) continue;
-      uint64_t *dst = ar + (size_t)(i == 1 ? 0 : i - 2) * ar_str;
-      if (used0) NUT_HIP(hipMemcpyAsync(dst, O[i] + abase0, used0 * 8, hipMemcpyDeviceToDevice, st));
-      if (used1) NUT_HIP(hipMemcpyAsync(dst + used0, B2[i] + ovf1, used1 * 8, hipMemcpyDeviceToDevice, st));
-    }
-    nut_agg_spec sa = s3;
-    sa.n = ar_rows;
-    sa.keys[0] = (const int64_t *)ar;
-    for (int j = 0; j < NUT_MAX_VALS; ++j)
-      if (vmap[j] >= 0) sa.val_col[vmap[j]] = ar + (size_t)(1 + vmap[j]) * ar_str;
-    // (partitioned whatever its size: the rows are the tails of many keys — up to one group
-    // per row — and the streaming path's global table would take every one of them by
-    // atomics: 4 ms for 8.7 M arena rows of the 1e9-row Zipf step)
-    const uint32_t path = c->gb_path, lv = c->gb_levels, opt = c->gb_optimistic;
-    const int64_t part = c->opt[NUT_OPT_GB_PARTITION];
-    c->opt[NUT_OPT_GB_PARTITION] = 1;
-    nut_groups *ga = nullptr;
-    uint64_t na_groups = 0;
-    e = nut_groupby(c, &sa, std::min<uint64_t>(ar_rows, group_hint), &ga);
-    c->opt[NUT_OPT_GB_PARTITION] = part;
-    c->gb_path = path, c->gb_levels = lv, c->gb_optimistic = opt;
-    if (!e) e = nut_groups_size(ga, &na_groups);
-    std::vector<int64_t> hk(na_groups);
-    std::vector<uint64_t> hw(na_groups * (size_t)na);
-    if (!e && na_groups) e = nut_groups_to_host(ga, hk.data(), hw.data(), na_groups);
-    nut_groups_free(ga);
-    if (e) return e;
-    done = fold_sorted_groups(keys_h, aggs_h, done, cap, hk, hw, g->kinds, na, &over);
+    if (f) return z.decline(NUT_GB_DECLINE_ARENA);  // a level-1 run found the arena full
+  if (ctl[1] & 4u) return z.decline(NUT_GB_DECLINE_TABLE);  // a partition outgrew its block's table
+  c->gb_overflow_rows = z.used0 + z.used1;
+  return NUT_OK;
+}
+
+// ---- the arenas' rows (heavy keys' excess, mostly) aggregated on their own and folded
+// into the ordered host result
+// (copied out of gp_data first — the arenas live there and the group-by may partition,
+// which takes gp_data — then one group-by over both levels' rows, on whichever path its
+// size picks)
+nut_status go_fold_arenas(GoState &z) {
+  nut_ctx *c = z.c;
+  hipStream_t st = z.st;
+  const uint64_t used0 = z.used0, used1 = z.used1;
+  const uint64_t ar_rows = used0 + used1, ar_str = (ar_rows + 31) & ~31ull;  // (arrays 256-B aligned: vector loads)
+  StreamMem arm;
+  nut_status e = arm.alloc(ar_str * 8 * (1 + (size_t)z.sc.nv), st);
+  if (e) return e;
+  uint64_t *arr[GP_MAX_ARR] = {};
+  for (int i = 1; i < z.narr; ++i) {
+    if (i == 2) continue;
+    uint64_t *dst = arr[i] = (uint64_t *)arm.p + (size_t)(i == 1 ? 0 : i - 2) * ar_str;
+    if (used0) NUT_HIP(hipMemcpyAsync(dst, z.O[i] + z.sz.abase0, used0 * 8, hipMemcpyDeviceToDevice, st));
+    if (used1) NUT_HIP(hipMemcpyAsync(dst + used0, z.B2[i] + z.l1.ovf1, used1 * 8, hipMemcpyDeviceToDevice, st));
   }
-  if (nh && !over) {
-    // heavy keys that joined no region (their level-0 partition was empty, or the region
-    // was full): folded here (result words: f64 MIN / MAX back from the table order)
-    std::vector<uint64_t> hw((size_t)nh * na);
-    NUT_HIP(hipMemcpyAsync(hw.data(), dheavy + nh, hw.size() * 8, hipMemcpyDeviceToHost, st));
-    NUT_HIP(hipStreamSynchronize(st));
-    std::vector<int64_t> fk;
-    std::vector<uint64_t> fw;
-    for (uint32_t j = 0; j < nh; ++j) {
-      if (hq[j] >= 0 && !miss[j]) continue;
-      fk.push_back(hkeys[j]);
-      for (int a = 0; a < na; ++a) {
-        const uint64_t x = hw[(size_t)j * na + a];
-        fw.push_back(g->kinds[a] == AK_MIN_F64 || g->kinds[a] == AK_MAX_F64 ? ord_to_f64(x) : x);
-      }
-    }
-    if (!fk.empty()) done = fold_sorted_groups(keys_h, aggs_h, done, cap, fk, fw, g->kinds, na, &over);
+  const nut_agg_spec sa = staged_spec(z.s, z.sc, 1, ar_rows, arr);
+  // (partitioned whatever its size: the rows are the tails of many keys — up to one group
+  // per row — and the streaming path's global table would take every one of them by
+  // atomics: 4 ms for 8.7 M arena rows of the 1e9-row Zipf step)
+  const uint32_t path = c->gb_path, lv = c->gb_levels, opt = c->gb_optimistic;
+  const int64_t part = c->opt[NUT_OPT_GB_PARTITION];
+  c->opt[NUT_OPT_GB_PARTITION] = 1;
+  nut_groups *ga = nullptr;
+  uint64_t na_groups = 0;
+  e = nut_groupby(c, &sa, std::min<uint64_t>(ar_rows, z.group_hint), &ga);
+  c->opt[NUT_OPT_GB_PARTITION] = part;
+  c->gb_path = path, c->gb_levels = lv, c->gb_optimistic = opt;
+  if (!e) e = nut_groups_size(ga, &na_groups);
+  std::vector<int64_t> hk(na_groups);
+  std::vector<uint64_t> hw(na_groups * (size_t)z.na);
+  if (!e && na_groups) e = nut_groups_to_host(ga, hk.data(), hw.data(), na_groups);
+  nut_groups_free(ga);
+  if (e) return e;
+  z.done = fold_sorted_groups(z.keys_h, z.aggs_h, z.done, z.cap, hk, hw, z.g->kinds, z.na, &z.over);
+  return NUT_OK;
+}
+
+// ---- heavy keys that joined no region (their level-0 partition was empty, or the region
+// was full): folded here
+nut_status go_fold_heavy(GoState &z) {
+  std::vector<uint64_t> hw;
+  nut_status e = go_heavy_words(z, hw);
+  if (e) return e;
+  std::vector<int64_t> fk;
+  std::vector<uint64_t> fw;
+  for (uint32_t j = 0; j < z.nh; ++j) {
+    if (z.l1.hq[j] >= 0 && !z.miss[j]) continue;
+    fk.push_back(z.hv.keys[j]);
+    fw.insert(fw.end(), hw.begin() + (size_t)j * z.na, hw.begin() + (size_t)(j + 1) * z.na);
   }
-  *n_out = done;
-  if (over) return fail(NUT_ERR_CAPACITY, "nut_groupby_to_host: capacity " + std::to_string(cap) + " < " +
-                                              std::to_string(done) + " groups");
+  if (!fk.empty()) z.done = fold_sorted_groups(z.keys_h, z.aggs_h, z.done, z.cap, fk, fw, z.g->kinds, z.na, &z.over);
+  return NUT_OK;
+}
+
+nut_status groupby_ordered(nut_ctx *c, const nut_agg_spec *s, uint64_t group_hint, int64_t *keys_h, uint64_t *aggs_h,
+                           uint64_t cap, uint64_t *n_out) {
+  GoState z(c, s, group_hint, keys_h, aggs_h, cap);
+  const uint64_t n = z.n;
+  const int na = z.na;
+  bool shape = s->nkeys == 1 && !s->prog_mode && s->npred == 0 && !s->key_prog[0].n && c->opt[NUT_OPT_GB_ORDERED] != 0 &&
+               c->opt[NUT_OPT_GB_DIRECT] != 0 && c->opt[NUT_OPT_GB_OPTIMISTIC] != 0 && c->opt[NUT_OPT_GB_PARTITION] != 0 &&
+               c->opt[NUT_OPT_GB_LEVELS] != 1 && c->opt[NUT_OPT_GB_DENSE] != 0 && na >= 1 && n >= (1ull << 24) &&
+               n >= 4 * group_hint && host_pinned_ptr(keys_h) && host_pinned_ptr(aggs_h) && cap > 0;
+  for (int a = 0; a < na && shape; ++a) shape = s->agg_op[a] == NUT_AGG_COUNT || s->agg_expr[a] == NUT_EX_COL;
+  // the 2^14 range cells split into a level-0 and a level-1 digit (NUT_OPT_GB_L0_BITS 6..8;
+  // default 7 + 7: level 0's runs twice as long as at 8 + 6 for level 1's half as long —
+  // same-box A/B at G = 1e7, 1e9 rows, three rounds: step 21.63-21.81 ms vs 22.44-22.56
+  // (8 + 6) and 22.48-22.56 (6 + 8), profiles/r04/groupby1e7/ab_l0bits.txt)
+  z.bits0 = c->opt[NUT_OPT_GB_L0_BITS] >= 6 && c->opt[NUT_OPT_GB_L0_BITS] <= 8 ? (int)c->opt[NUT_OPT_GB_L0_BITS] : 7;
+  z.bits1 = 14 - z.bits0;
+  z.lam = (double)group_hint / (double)(1 << (z.bits0 + z.bits1));
+  c->gb_overflow_rows = 0;
+  c->gb_decline = 0;
+  c->gb_heavy_keys = 0;
+  c->gb_heavy_rows = 0;
+  if (!shape || z.lam < 100 || ((uintptr_t)s->keys[0] & 15)) return z.decline(NUT_GB_DECLINE_SHAPE);
+  nut_status e;
+  if ((e = go_sample(z)) || (e = go_plan(z))) return e;
+  z.n0 = n;
+  if (z.nh && (e = go_heavy_pass(z))) return e;
+  c->gb_heavy_keys = z.nh;
+  c->gb_heavy_rows = n - z.n0;
+  if (z.nh && z.n0 == 0) {
+    // every row was a heavy key's (few distinct keys under a large group_hint): no row is
+    // left for the partition levels, and the heavy pass's groups are the whole result
+    // (hkeys ascending, every one seen in the data)
+    std::vector<uint64_t> hw;
+    if ((e = go_heavy_words(z, hw))) return e;
+    *n_out = fold_sorted_groups(keys_h, aggs_h, 0, cap, z.hv.keys, hw, z.g->kinds, na, &z.over);
+    if (z.over) return fail(NUT_ERR_CAPACITY, "nut_groupby_to_host: capacity " + std::to_string(cap) + " < " +
+                                                  std::to_string(z.nh) + " groups");
+    return NUT_OK;
+  }
+  if ((e = go_level0(z)) || (e = go_plan_level1(z)) || (e = go_upload(z)) || (e = go_streams(z))) return e;
+  // every chunk queued (nothing waits for the host)
+  for (uint32_t j = 0; j < z.l1.nch(); ++j)
+    if ((e = go_enqueue(z, j))) return e;
+  if ((e = go_drain(z))) return e;
+  if (z.used0 + z.used1 && !z.over && (e = go_fold_arenas(z))) return e;
+  if (z.nh && !z.over && (e = go_fold_heavy(z))) return e;
+  *n_out = z.done;
+  if (z.over) return fail(NUT_ERR_CAPACITY, "nut_groupby_to_host: capacity " + std::to_string(cap) + " < " +
+                                                std::to_string(z.done) + " groups");
   return NUT_OK;
 }
 

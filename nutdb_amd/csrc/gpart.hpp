@@ -10,53 +10,25 @@
 // SEGMENT mode, one workgroup per partition: every group of a partition lives in that
 // workgroup's LDS table, and the block-end merge into the global table inserts each group
 // once, with no contention (partitions hold disjoint keys).
+// (GpSeg, GpRange and the scatter tile's size live in go_plan.hpp, which the host shares.)
 #pragma once
 
 #include "common.hpp"
+#include "go_plan.hpp"
 #include "gtable.hpp"
 
 namespace nut {
 
-constexpr int GP_THREADS = 512;
-constexpr int GP_ITEMS = 16;
-constexpr uint32_t GP_TILE = GP_THREADS * GP_ITEMS;  // 8192 records per scatter tile
 constexpr int GP_HTHREADS = 256;
 constexpr uint32_t GP_HTILE = 1u << 18;              // records per histogram tile (one flush each)
 constexpr int GP_HLOADS = 16;                        // keys in flight per lane in the histogram
 constexpr int GP_BINS = 256;
 constexpr int GP_MAX_ARR = 3 + NUT_MAX_VALS;         // hash, k1, k2, value arrays
 
-struct GpSeg {  // records [start, start + count) of the current buffer
-  uint64_t start, count;
-  uint32_t tile0, pad;  // first tile of the segment in the launch's tile table
-  // capped layout (no histogram pass): digit d of this segment owns output rows
-  // [obase + d * ocap, obase + (d + 1) * ocap)
-  uint64_t obase = 0, ocap = 0;
-};
-
 struct GpArrays {
   const uint64_t *src[GP_MAX_ARR];  // [0] unused, [1] k1, [2] k2 (two keys), values
   uint64_t *dst[GP_MAX_ARR];
   int narr;
-};
-
-// Range digits (the ordered group-by, aggregate.hip groupby_ordered): keys mapped
-// monotonically onto 2^14 cells over a sampled range [lo, lo + span] (signed order; keys
-// outside are clamped to the end cells, so the order holds and only the balance suffers):
-// x = (k ^ 2^63) - lo, clamped to [0, span]; cell = mulhi((x >> t), mul) with mul =
-// floor(2^46 / ((span >> t) + 1)).  With the cells split into bits0 + bits1 digits
-// (NUT_OPT_GB_L0_BITS, default 7 + 7), level 0's digit is cell >> bits1 and level 1's
-// cell & (2^bits1 - 1), so the partitions are in key order.  (The scatter kernel's RANGE
-// template flag chooses these digits over the hash's; t is the range shift, 0 included.)
-struct GpRange {
-  uint64_t lo, span;
-  uint32_t mul;
-  int t;  // x's shift: (span >> t) < 2^32
-  __host__ __device__ __forceinline__ uint32_t cell(uint64_t k) const {
-    uint64_t x = (k ^ 0x8000000000000000ull) - lo;
-    x = (k ^ 0x8000000000000000ull) < lo ? 0 : (x > span ? span : x);
-    return (uint32_t)(((uint64_t)(uint32_t)(x >> t) * mul) >> 32);  // (v_mul_hi_u32)
-  }
 };
 
 // the partition digit: a byte of the key tuple's owner hash (recomputed, never stored);
@@ -355,7 +327,6 @@ __global__ __launch_bounds__(1024) void go_heavy_insert_kernel(const int64_t *__
 // (keys of ~1/2 to 2 cell shares), so both levels then lay their regions out from these
 // exact counts — no capped regions, no overflow arenas — for 8 B per kept row.
 constexpr int GO_HIST_THREADS = 512;
-constexpr uint32_t GO_CELLS = 1u << 14;
 __global__ __launch_bounds__(GO_HIST_THREADS) void go_cell_hist_kernel(const uint64_t *__restrict__ k,
                                                                        const uint64_t *__restrict__ count,
                                                                        uint64_t chunk, GpRange rg,

@@ -9,19 +9,15 @@
 // lookup), their rows fold into LDS accumulators (merged into device words once per
 // workgroup), and every other row is copied, compacted, to the arrays the partition levels
 // then read.  scripts/tune/hk_tune.hip times it against a copy of the same arrays.
+// (The HK_* constants, hk_slot and the host's hk_cuckoo live in go_plan.hpp.)
 #pragma once
 
 #include "agg_ops.hpp"
 #include "common.hpp"
+#include "go_plan.hpp"
 #include "gtable.hpp"
 
 namespace nut {
-
-constexpr int HK_THREADS = 256, HK_ITEMS = 8;
-constexpr uint32_t HK_TILE = HK_THREADS * HK_ITEMS;  // rows per tile
-constexpr int HK_MAX = 2048;                         // heavy keys at most
-constexpr int HK_SLOTS = 8192;                       // cuckoo slots (load <= 1/4), host-built
-constexpr int HK_WORDS = 2048;                       // heavy keys x aggregates at most (16 KB)
 
 struct HkArgs {
   const uint64_t *key;
@@ -40,33 +36,6 @@ struct HkArgs {
   uint64_t *hagg;                     // [h x na] table-encoded words, initialised to agg_init
   uint64_t *count;                    // [gridDim.x] rows each workgroup kept
 };
-
-// a key's two cuckoo slots (the host places every heavy key in one of them: hk_cuckoo)
-__host__ __device__ __forceinline__ uint32_t hk_slot(uint64_t k, uint64_t seed) {
-  return (uint32_t)(mix64(k ^ seed) >> 32) & (HK_SLOTS - 1);
-}
-
-// host: a cuckoo table of the h keys (slot = key index + 1); false if some key found no
-// place (the caller retries with other seeds)
-inline bool hk_cuckoo(const int64_t *hk, uint32_t h, uint64_t s1, uint64_t s2, uint16_t *slot) {
-  for (int i = 0; i < HK_SLOTS; ++i) slot[i] = 0;
-  for (uint32_t j = 0; j < h; ++j) {
-    uint16_t cur = (uint16_t)(j + 1);
-    uint32_t pos = hk_slot((uint64_t)hk[j], s1);
-    int steps = 0;
-    for (;;) {
-      const uint16_t old = slot[pos];
-      slot[pos] = cur;
-      if (!old) break;
-      if (++steps > 1000) return false;
-      cur = old;  // the evicted key moves to its other slot
-      const uint64_t k = (uint64_t)hk[old - 1];
-      const uint32_t a = hk_slot(k, s1), b = hk_slot(k, s2);
-      pos = pos == a ? b : a;
-    }
-  }
-  return true;
-}
 
 // a raw buffer resource over `bytes` bytes from p (stride 0; stores past `bytes` are
 // discarded by the bounds check — how a dropped row's store writes nothing)
