@@ -1070,6 +1070,7 @@ struct GoState {
   std::vector<uint64_t> miss;         // heavy keys whose partition's region was full
   uint64_t done = 0;                  // groups already sent to the host
   bool over = false;
+  std::vector<uint64_t> dcnt;         // over: the groups of every final partition's region (go_count_arenas)
   // released on every return, after the copy stream has drained (it reads `res` and
   // waits on the events)
   struct Drain {
@@ -1457,6 +1458,10 @@ nut_status go_drain(GoState &z) {
   z.miss.resize(nh);
   NUT_HIP(hipMemcpyAsync(flags.data(), z.dcur + z.l1.nparts, nch * 8, hipMemcpyDeviceToHost, st));
   if (nh) NUT_HIP(hipMemcpyAsync(z.miss.data(), z.dmiss, (size_t)nh * 8, hipMemcpyDeviceToHost, st));
+  if (z.over) {  // the regions' group counts: what go_count_arenas looks the arenas' keys up in
+    z.dcnt.resize(z.l1.nparts);
+    NUT_HIP(hipMemcpyAsync(z.dcnt.data(), z.dcount, z.l1.nparts * 8, hipMemcpyDeviceToHost, st));
+  }
   uint32_t ctl[4];
   NUT_HIP(hipMemcpyAsync(c->host_pinned, z.g->gt.ctl, 16, hipMemcpyDeviceToHost, st));
   NUT_HIP(hipMemcpyAsync(c->host_pinned + 2, z.darena(), 16, hipMemcpyDeviceToHost, st));
@@ -1477,7 +1482,7 @@ nut_status go_drain(GoState &z) {
 // (copied out of gp_data first — the arenas live there and the group-by may partition,
 // which takes gp_data — then one group-by over both levels' rows, on whichever path its
 // size picks)
-nut_status go_fold_arenas(GoState &z) {
+nut_status go_arena_groups(GoState &z, std::vector<int64_t> &hk, std::vector<uint64_t> &hw) {
   nut_ctx *c = z.c;
   hipStream_t st = z.st;
   const uint64_t used0 = z.used0, used1 = z.used1;
@@ -1505,12 +1510,57 @@ nut_status go_fold_arenas(GoState &z) {
   c->opt[NUT_OPT_GB_PARTITION] = part;
   c->gb_path = path, c->gb_levels = lv, c->gb_optimistic = opt;
   if (!e) e = nut_groups_size(ga, &na_groups);
-  std::vector<int64_t> hk(na_groups);
-  std::vector<uint64_t> hw(na_groups * (size_t)z.na);
+  hk.resize(na_groups);
+  hw.resize(na_groups * (size_t)z.na);
   if (!e && na_groups) e = nut_groups_to_host(ga, hk.data(), hw.data(), na_groups);
   nut_groups_free(ga);
+  return e;
+}
+nut_status go_fold_arenas(GoState &z) {
+  std::vector<int64_t> hk;
+  std::vector<uint64_t> hw;
+  nut_status e = go_arena_groups(z, hk, hw);
   if (e) return e;
   z.done = fold_sorted_groups(z.keys_h, z.aggs_h, z.done, z.cap, hk, hw, z.g->kinds, z.na, &z.over);
+  return NUT_OK;
+}
+
+// ---- the result outgrew cap in the device-ordered part (the host holds a part of it, the
+// result buffer the first cap groups): *n_out is still the room needed (nutexec.h), so the
+// arenas' groups that the skipped fold would have ADDED are counted — those whose key is in
+// no region of the aggregation's table (a key's region follows from its range cell, as
+// go_level1 places the heavy keys; z.dcnt: go_drain read the regions' counts before the
+// arenas' group-by could take gp_meta).  No row moves.
+nut_status go_count_arenas(GoState &z) {
+  std::vector<int64_t> hk;
+  std::vector<uint64_t> hw;
+  nut_status e = go_arena_groups(z, hk, hw);
+  if (e) return e;
+  const uint32_t nb1 = 1u << z.bits1;
+  std::vector<int64_t> idx0((size_t)1 << z.bits0, -1);
+  for (uint32_t i = 0; i < z.l0.dig0.size(); ++i) idx0[z.l0.dig0[i]] = i;
+  std::vector<uint64_t> region;
+  int64_t have = -1;  // the region in `region` (hk ascending: a key's region never precedes the one before)
+  for (int64_t k : hk) {
+    const uint32_t cell = z.rg.cell((uint64_t)k);
+    const int64_t i0 = idx0[cell >> z.bits1];
+    bool found = false;
+    if (i0 >= 0) {
+      const int64_t q = i0 * nb1 + (cell & (nb1 - 1));
+      if (q != have) {
+        region.resize(std::min<uint64_t>(z.dcnt[q], z.dregion));
+        if (!region.empty()) {
+          NUT_HIP(hipMemcpyAsync(region.data(), z.g->gt.slot + (uint64_t)q * z.dregion, region.size() * 8,
+                                 hipMemcpyDeviceToHost, z.st));
+          NUT_HIP(hipStreamSynchronize(z.st));
+        }
+        std::sort(region.begin(), region.end());  // (once per region: many arena keys may share it)
+        have = q;
+      }
+      found = std::binary_search(region.begin(), region.end(), (uint64_t)k);
+    }
+    if (!found) ++z.done;
+  }
   return NUT_OK;
 }
 
@@ -1527,7 +1577,10 @@ nut_status go_fold_heavy(GoState &z) {
     fk.push_back(z.hv.keys[j]);
     fw.insert(fw.end(), hw.begin() + (size_t)j * z.na, hw.begin() + (size_t)(j + 1) * z.na);
   }
-  if (!fk.empty()) z.done = fold_sorted_groups(z.keys_h, z.aggs_h, z.done, z.cap, fk, fw, z.g->kinds, z.na, &z.over);
+  // (over: an earlier stage outgrew cap and the host result is partial — these keys are in no
+  // region and in no arena, so each one is a group more: counted, not folded)
+  if (z.over) z.done += fk.size();
+  else if (!fk.empty()) z.done = fold_sorted_groups(z.keys_h, z.aggs_h, z.done, z.cap, fk, fw, z.g->kinds, z.na, &z.over);
   return NUT_OK;
 }
 
@@ -1575,8 +1628,9 @@ nut_status groupby_ordered(nut_ctx *c, const nut_agg_spec *s, uint64_t group_hin
   for (uint32_t j = 0; j < z.l1.nch(); ++j)
     if ((e = go_enqueue(z, j))) return e;
   if ((e = go_drain(z))) return e;
-  if (z.used0 + z.used1 && !z.over && (e = go_fold_arenas(z))) return e;
-  if (z.nh && !z.over && (e = go_fold_heavy(z))) return e;
+  // (a stage that outgrows cap stops the moves, not the count: *n_out is the room needed)
+  if (z.used0 + z.used1 && (e = z.over ? go_count_arenas(z) : go_fold_arenas(z))) return e;
+  if (z.nh && (e = go_fold_heavy(z))) return e;
   *n_out = z.done;
   if (z.over) return fail(NUT_ERR_CAPACITY, "nut_groupby_to_host: capacity " + std::to_string(cap) + " < " +
                                                 std::to_string(z.done) + " groups");

@@ -16,10 +16,17 @@
 //   l1 <exact> <bits0> <slack1> <b2rows> <l1_threads>
 //                                         -> l1 why ovf1 acap1 nparts; cb, tile0, ntile, tiles, s2 (5 words each),
 //                                            init, rend, hq
+// Bulk commands for tests/test_gorder_shapes_cpu.py (whole columns, read from binary files of int64):
+//   samplef <file>                        -> samplef 0 total min max   (the sample: the file's first 65536 keys)
+//   hist <file> <count>                   -> hist 0 kept heavy nonzero; cells: cell rows per non-empty cell
+//                                            (the keys that are not heavy keys, counted per range cell: sets `counts`)
+//   slots <k> then k keys                 -> slots 0 k; sl: key a slot[a] b slot[b] per key (the heavy pass's lookups)
+//   grid <n> <num_cus> <per_cu>           -> grid why ntiles hgrid chunk
 #include <inttypes.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "go_plan.hpp"
@@ -165,6 +172,64 @@ int main() {
       line("init", l1.init);
       line("rend", l1.rend);
       line("hq", l1.hq);
+    } else if (!strcmp(cmd, "samplef")) {
+      char path[1024];
+      if (scanf("%1023s", path) != 1) return 2;
+      FILE *f = fopen(path, "rb");
+      if (!f) return 5;
+      std::vector<int64_t> smp(kGoSample);
+      smp.resize(fread(smp.data(), 8, kGoSample, f));
+      fclose(f);
+      if (smp.empty()) return 5;
+      go_sample_table(smp, &tab);
+      const auto mm = std::minmax_element(smp.begin(), smp.end());
+      printf("samplef 0 %zu %" PRId64 " %" PRId64 "\n", smp.size(), *mm.first, *mm.second);
+    } else if (!strcmp(cmd, "hist")) {
+      char path[1024];
+      uint64_t count;
+      if (scanf("%1023s", path) != 1 || !u64(&count)) return 2;
+      FILE *f = fopen(path, "rb");
+      if (!f) return 5;
+      cells.assign(GO_CELLS, 0);
+      uint64_t kept = 0, heavy = 0, nonzero = 0;
+      std::vector<int64_t> buf(1 << 16);
+      while (count) {
+        const size_t got = fread(buf.data(), 8, (size_t)std::min<uint64_t>(count, buf.size()), f);
+        if (!got) break;
+        count -= got;
+        for (size_t i = 0; i < got; ++i) {
+          if (std::binary_search(hv.keys.begin(), hv.keys.end(), buf[i])) {
+            ++heavy;
+          } else {
+            ++kept;
+            ++cells[rg.cell((uint64_t)buf[i])];
+          }
+        }
+      }
+      fclose(f);
+      if (count) return 5;
+      for (uint64_t x : cells) nonzero += x != 0;
+      printf("hist 0 %" PRIu64 " %" PRIu64 " %" PRIu64 "\ncells", kept, heavy, nonzero);
+      for (uint32_t q = 0; q < GO_CELLS; ++q)
+        if (cells[q]) printf(" %u %" PRIu64, q, cells[q]);
+      printf("\n");
+    } else if (!strcmp(cmd, "slots")) {
+      uint64_t k;
+      if (!u64(&k) || hv.slot.size() != HK_SLOTS) return 2;
+      printf("slots 0 %" PRIu64 "\n", k);
+      for (uint64_t i = 0; i < k; ++i) {
+        int64_t key;
+        if (!i64(&key)) return 2;
+        const uint32_t a = hk_slot((uint64_t)key, hv.seed1), b = hk_slot((uint64_t)key, hv.seed2);
+        printf("sl %" PRId64 " %u %u %u %u\n", key, a, (unsigned)hv.slot[a], b, (unsigned)hv.slot[b]);
+      }
+    } else if (!strcmp(cmd, "grid")) {
+      uint64_t n;
+      int cus, per_cu;
+      if (!u64(&n) || scanf("%d %d", &cus, &per_cu) != 2) return 2;
+      GoHeavyGrid hg;
+      const uint32_t why = go_heavy_grid(n, cus, per_cu, &hg);
+      printf("grid %u %" PRIu64 " %" PRIu64 " %" PRIu64 "\n", why, hg.ntiles, hg.hgrid, hg.chunk);
     } else {
       return 3;
     }
